@@ -21,6 +21,13 @@ uint8 -> 3000x3000 bilinear upsample), forward, loss, zero_grad, backward
 exactly K steps bracketed by barrier + synchronize; the elapsed time is the
 MAX over ranks.  Rank 0 prints one JSON line.
 
+A plain run does only that: set up, warm up, time the K steps, print.  ``--full``
+adds everything else the benchmark measures (the post-timing all-reduce
+bandwidth probe at world > 1, ``config.allreduce_probe``).  ``--dump-outputs DIR``
+writes what the last timed step computed (loss, logits, the state dict after the
+update, the gradients) as ``DIR/<name>.npy``; model, data and sample indices are
+seeded, so two builds run with the same arguments can be compared file by file.
+
 Default multi-GPU stack: this package's RCCL communicator (``rccl-native``:
 own comm stream, non-blocking init with a bounded wait, watchdog) and the C++
 gradient reducer; ``--backend rccl`` selects torch's ProcessGroupNCCL instead.
@@ -143,9 +150,18 @@ def _parser():
     ap.add_argument("--prefetch-at", choices=["head", "conv2_bwd"], default="head",
                     help="where --prefetch queues the next batch: beside the head forward / backward (memory-"
                          "bound, room for the pipeline's workgroups) or beside the conv2 backward (round 2: no room)")
-    ap.add_argument("--allreduce-probe", action=argparse.BooleanOptionalAction, default=True,
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline run, everything else the benchmark measures (today: the "
+                         "post-timing all-reduce probe at world > 1, --allreduce-probe); a plain run does only "
+                         "what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step computed -- the loss, the "
+                         "logits, every parameter and buffer after the update and every gradient -- as "
+                         "DIR/<name>.npy (float32; a tensor above 1 M elements as a fixed seeded sample of 1 M)")
+    ap.add_argument("--allreduce-probe", action=argparse.BooleanOptionalAction, default=None,
                     help="world > 1: after the timed steps, time a few all-reduces over the same communicator "
-                         "and report their bus bandwidth in config.allreduce_probe (outside the timed region)")
+                         "and report their bus bandwidth in config.allreduce_probe (outside the timed region); "
+                         "default: on with --full, else off")
     ap.add_argument("--sim-comm-us", type=int, default=0,
                     help="1-GPU rehearsal of a collective's CU footprint: after each forward, hold "
                          "--sim-comm-ctas workgroups of RCCL's size (256 threads, 19.7 KB LDS) for this many "
@@ -293,6 +309,35 @@ def _allreduce_probe(tdist, device, world, on_gpu):
                     "busbw_GBps": round(2 * (world - 1) / world * nbytes / dt / 1e9, 2)})
         del t
     return out
+
+
+_DUMP_SAMPLE = 1 << 20  # elements kept of a larger tensor (the 180 M-element fc weight at 3000x3000)
+
+
+def _dump_outputs(out_dir: str, model, loss, logits) -> dict:
+    """What the last timed step handed its caller, as ``out_dir/<name>.npy`` (float32): the loss,
+    the logits, the state dict after the update (``state.<key>``) and every gradient left in
+    ``.grad`` (``grad.<key>``; a parameter stepped inside its backward kernel has none).  A tensor
+    above ``_DUMP_SAMPLE`` elements is written as its elements at a fixed seeded set of flat
+    indices (the same for a given shape in every run), so the files of two builds run with the
+    same arguments compare element for element.  Returns {name: elements written}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    named = {"loss": loss, "logits": logits}
+    named.update({f"state.{k}": v for k, v in model.state_dict().items()})
+    named.update({f"grad.{k}": p.grad for k, p in model.named_parameters() if p.grad is not None})
+    written = {}
+    for name, t in named.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > _DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(20240229)
+            idx = torch.randint(t.numel(), (_DUMP_SAMPLE,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        a = t.to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = int(a.size)
+    return written
 
 
 _BUS = {  # bytes on the busiest link per byte counted (nccl-tests "busbw" conventions)
@@ -804,6 +849,10 @@ def _attempt(args, world, rank, backend, grad_exchange, reserve, backend_label, 
         n = int(args.sim_sdma_mb * 1e6) // 4
         sdma = (torch.cuda.Stream(device), torch.empty(n, device=device), torch.zeros(n, device=device))
 
+    # --dump-outputs: the last timed step's logits are kept (rank 0) for the dump after the timing
+    last_step = args.warmup + args.steps - 1 if args.dump_outputs and rank == 0 and args.steps > 0 else -1
+    last_logits = []
+
     def step(i):
         j = i % pool
         if i in pending:
@@ -820,6 +869,8 @@ def _attempt(args, world, rank, backend, grad_exchange, reserve, backend_label, 
             # the loss and dlogits formed by the head forward's finalizing workgroup with the logits
             convnet_fused.attach_labels(images, labels)
         out = ddp(images)
+        if i == last_step:
+            last_logits.append(out.detach())
         if sim_stream is not None:
             sim_stream.wait_stream(torch.cuda.current_stream(device))
             with torch.cuda.stream(sim_stream):
@@ -876,8 +927,13 @@ def _attempt(args, world, rank, backend, grad_exchange, reserve, backend_label, 
         from torch_distributed_sandbox_amd.utils.streams import release_streams
 
         release_streams()
+    dumped = None
+    if last_logits:
+        phase[0] = f"attempt {k} ({backend}): dump outputs"
+        dumped = _dump_outputs(args.dump_outputs, model, loss, last_logits[0])
     phase[0] = f"attempt {k} ({backend}): report"
-    probe = _allreduce_probe(tdist, device, world, on_gpu) if world > 1 and args.allreduce_probe else None
+    want_probe = args.full if args.allreduce_probe is None else args.allreduce_probe
+    probe = _allreduce_probe(tdist, device, world, on_gpu) if world > 1 and want_probe else None
     ms = 1e3 * elapsed / max(1, args.steps)
     imgs_per_sec = world * B * args.steps / elapsed
     if rank == 0:
@@ -919,6 +975,8 @@ def _attempt(args, world, rank, backend, grad_exchange, reserve, backend_label, 
             config["preflight"] = preflight
         if probe is not None:
             config["allreduce_probe"] = probe
+        if dumped is not None:
+            config["dump_outputs"] = dumped
         if sdma is not None:
             config["sim_sdma"] = {"MB": args.sim_sdma_mb, "engine": args.sim_sdma_engine}
         if sim_stream is not None:

@@ -34,6 +34,28 @@ def test_bench_one_gpu_small(gpu, prefetch):
     assert r["config"]["input_moments"] == "upsample" and r["config"]["loss_in_head"] is True
 
 
+def test_bench_dump_outputs(gpu, tmp_path):
+    """--dump-outputs on the fused GPU plan: the last timed step's loss, logits, state dict and
+    gradients as float32 .npy files (the fc weight, stepped inside the head backward, as a fixed
+    sample and without a gradient file)."""
+    import numpy as np
+
+    r = _bench(["--image-size", "512", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert r["steps"] == 2 and r["ms_per_step"] > 0
+    arrs = {f[:-4]: np.load(tmp_path / f) for f in sorted(os.listdir(tmp_path))}
+    assert {k: int(v.size) for k, v in arrs.items()} == r["config"]["dump_outputs"]
+    assert {"loss", "logits", "state.fc.weight", "state.fc.bias", "state.layer1.0.weight",
+            "state.layer2.0.weight", "state.layer2.1.running_var"} <= set(arrs)
+    assert arrs["logits"].size == 5 * 10 and arrs["state.fc.weight"].size == 1 << 20
+    assert abs(float(arrs["loss"][0]) - r["config"]["final_loss"]) <= 1e-6 * max(1.0, abs(r["config"]["final_loss"]))
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+    # loss and logits are one step's: a cross-entropy is at least mean(logsumexp - largest logit)
+    # of its own logits (the numerics themselves are tests/test_fused_gpu.py's)
+    lg = arrs["logits"].reshape(5, 10).astype(np.float64)
+    lse = np.log(np.exp(lg - lg.max(1, keepdims=True)).sum(1)) + lg.max(1)
+    assert float(arrs["loss"][0]) >= float((lse - lg.max(1)).mean()) - 1e-4
+
+
 @pytest.mark.parametrize("exchange", ["auto", "allreduce"])
 def test_bench_self_spawn_shared_device(gpu, exchange):
     r = _bench(["--gpus", "2", "--backend", "gloo", "--shared-device", "--image-size", "512", "--steps", "2",

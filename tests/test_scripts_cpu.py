@@ -94,7 +94,8 @@ def test_bench_self_spawns_ranks_cpu():
     """`python bench.py --gpus 2` with no external launcher starts both ranks itself
     (reference: mp.spawn(train, nprocs=args.gpus), mnist_distributed.py:127) and rank 0
     prints exactly one JSON line for the whole job."""
-    p = _run(["bench.py", "--gpus", "2", "--device", "cpu", "--image-size", "32", "--steps", "2", "--warmup", "1"])
+    p = _run(["bench.py", "--gpus", "2", "--device", "cpu", "--image-size", "32", "--steps", "2", "--warmup", "1",
+              "--full"])
     assert p.returncode == 0, p.stderr
     recs = _json_lines(p.stdout)
     assert len(recs) == 1
@@ -106,6 +107,52 @@ def test_bench_self_spawns_ranks_cpu():
     assert r["dtype"] == "fp32 (CPU rehearsal: torch ops)"
     (pr,) = r["config"]["allreduce_probe"]  # post-timing all-reduce bandwidth over the same communicator
     assert pr["MB"] > 0 and pr["ms"] > 0 and pr["busbw_GBps"] > 0
+
+
+def test_bench_plain_run_options():
+    """A plain run measures the headline only: everything else is behind --full (off by default);
+    an explicit --[no-]allreduce-probe still decides for itself."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench._parser().parse_args([])
+    assert a.full is False and a.allreduce_probe is None and a.dump_outputs is None and not a.step_times
+    assert bench._parser().parse_args(["--full"]).full is True
+    assert bench._parser().parse_args(["--full", "--no-allreduce-probe"]).allreduce_probe is False
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs writes what the last timed step computed (loss, logits, the state dict
+    after the update, the gradients) as float32 .npy files; the same arguments give the same
+    inputs, so two runs agree file by file.  A tensor above bench._DUMP_SAMPLE elements is a
+    fixed sample of that many."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    runs = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        # 384^2: the fc weight (10 x 32 x 96 x 96 = 2.9 M elements) is above the sample size
+        p = _run(["bench.py", "--gpus", "1", "--device", "cpu", "--image-size", "384", "--batch-size", "2",
+                  "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        (r,) = _json_lines(p.stdout)
+        assert r["steps"] == 2 and r["ms_per_step"] > 0 and r["value"] > 0
+        arrs = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert {k: int(v.size) for k, v in arrs.items()} == r["config"]["dump_outputs"]
+        runs.append((r, arrs))
+    (r, a), (_, b) = runs
+    assert {"loss", "logits", "state.fc.weight", "state.fc.bias", "state.layer1.0.weight", "state.layer2.0.weight",
+            "state.layer1.1.running_mean", "grad.layer1.0.weight"} <= set(a)
+    assert a["logits"].size == 2 * 10 and a["loss"].size == 1 and a["state.fc.weight"].size == bench._DUMP_SAMPLE
+    assert abs(float(a["loss"][0]) - r["config"]["final_loss"]) <= 1e-6 * max(1.0, abs(r["config"]["final_loss"]))
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert set(a) == set(b)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert a[k].shape == b[k].shape and np.allclose(a[k], b[k], rtol=1e-5, atol=1e-7), k
 
 
 def test_bench_self_spawn_native_host_backend_cpu():
