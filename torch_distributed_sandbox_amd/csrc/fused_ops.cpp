@@ -625,6 +625,43 @@ void head_update_pooled(const Tensor& dl_all, const Tensor& ya_all, const Tensor
   check_launches("head_update_pooled");
 }
 
+// The shard form (the sharded exchange's "pooled-sharded" source): this rank owns the fc columns of
+// channels [c0, c1) and holds every rank's ya planes of those channels, ya_sh [W, B, c1-c0, PB].
+// Same modes; only those columns of wfc / out are read or written, bitwise the columns
+// head_update_pooled forms from the full ya_all (head_pb.hip head_upd_pb_shard_kernel).
+void head_update_pooled_shard(const Tensor& dl_all, const Tensor& ya_sh, const Tensor& rec_all, const Tensor& wfc,
+                              const c10::optional<Tensor>& out, int64_t P, int64_t c0, int64_t c1, double scale,
+                              double lr, int64_t mode) {
+  TORCH_CHECK(c0 >= 0 && c0 < c1 && c1 <= 32, "head_update_pooled_shard: needs 0 <= c0 < c1 <= 32");
+  TORCH_CHECK(ya_sh.dim() == 4 && ya_sh.size(2) == c1 - c0, "head_update_pooled_shard: ya_sh must be [W,B,c1-c0,PB]");
+  const int64_t Wr = ya_sh.size(0), B = ya_sh.size(1), Q = P / 2;
+  TORCH_CHECK(Q >= 4 && B >= 1 && B <= 8, "head_update_pooled_shard: needs P/2 >= 4 and 1 <= B <= 8 images per rank");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "head_update_pooled_shard: mode 0 (update), 1 (=) or 2 (+=)");
+  need(ya_sh, at::kHalf, {Wr, B, c1 - c0, pb_plane(P)}, "ya_sh");
+  need(rec_all, at::kFloat, {Wr, 128}, "rec_all");
+  TORCH_CHECK(wfc.dim() == 2 && wfc.size(1) == 32 * Q * Q && wfc.size(0) >= 1 && wfc.size(0) <= 10,
+              "fc.weight must be [<=10, 32*Q*Q]");
+  const int64_t NC = wfc.size(0);
+  need(wfc, at::kFloat, {NC, 32 * Q * Q}, "fc.weight");
+  need(dl_all, at::kFloat, {Wr * B, NC}, "dl_all");
+  float* o = wfc.data_ptr<float>();
+  if (mode != 0) {
+    TORCH_CHECK(out.has_value() && out->defined(), "head_update_pooled_shard: modes 1 and 2 write into out");
+    need(*out, at::kFloat, {NC, 32 * Q * Q}, "out (dW)");
+    o = out->data_ptr<float>();
+  } else {
+    TORCH_CHECK(lr > 0.0, "head_update_pooled_shard: mode 0 needs lr > 0");
+  }
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(o) % 16 == 0 && reinterpret_cast<uintptr_t>(wfc.data_ptr()) % 16 == 0,
+              "head_update_pooled_shard: fc.weight and out must be 16-B aligned");
+  c10::DeviceGuard guard(wfc.device());
+  const int rc = tds_head_upd_pb_shard(ya_out(ya_sh), rec_all.data_ptr<float>(), (int)Wr, dl_all.data_ptr<float>(),
+                                       wfc.data_ptr<float>(), o, (int)B, (int)Q, (int)NC, (int)c0, (int)c1,
+                                       (float)scale, (float)lr, (int)mode, stream_of(wfc));
+  TORCH_CHECK(rc == 0, "head_update_pooled_shard: unsupported shape");
+  check_launches("head_update_pooled_shard");
+}
+
 // ---------------------------------------------------------------- head forward (BN2 finalize + fc)
 // returns (logits, stats2 [mean32|invstd32], aff2 [a32|b32])
 std::tuple<Tensor, Tensor, Tensor> fused_head_forward(
@@ -1171,6 +1208,10 @@ TORCH_LIBRARY_FRAGMENT(tdsa, m) {
       "head_update_pooled(Tensor dl_all, Tensor ya_all, Tensor rec_all, Tensor(a!) wfc, Tensor(b!)? out, int P, "
       "float scale, float lr, int mode) -> ()",
       &head_update_pooled);
+  m.def(
+      "head_update_pooled_shard(Tensor dl_all, Tensor ya_sh, Tensor rec_all, Tensor(a!) wfc, Tensor(b!)? out, int P, "
+      "int c0, int c1, float scale, float lr, int mode) -> ()",
+      &head_update_pooled_shard);
   m.def("mag_numel(int B, int P) -> int", &mag_numel);
   m.def("mag_ypart_count() -> int", &mag_ypart_count);
   m.def("conv2_bwd_clock_dump(int nwg) -> Tensor", &conv2_bwd_clock_dump);

@@ -142,6 +142,25 @@ struct HPRow {
 // 4 consecutive floats at any dword alignment (one global_load_dwordx4)
 __device__ __forceinline__ float4 hp_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
+// re-align the shifted edge groups of a chunk's loaded weight 4-groups (HPRow: sh, nvalid), zero what
+// lies outside the image and classes >= NC; wave-uniformly skipped for interior chunks with all
+// classes present
+__device__ __forceinline__ void hp_fix_w(float4 (&w)[10], int sh, int nvalid, int NC) {
+  if (NC == 10 && __builtin_amdgcn_ballot_w64(sh != 0 || nvalid != 4) == 0) return;
+#pragma unroll
+  for (int j = 0; j < 10; ++j) {
+    const float e[4] = {w[j].x, w[j].y, w[j].z, w[j].w};
+    float o[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float v = e[k];
+      if (sh > 0) v = (k + sh < 4) ? e[(k + sh) & 3] : 0.f;
+      o[k] = (j < NC && k < nvalid) ? v : 0.f;
+    }
+    w[j] = make_float4(o[0], o[1], o[2], o[3]);
+  }
+}
+
 // loads of one chunk: ya 4 fp16 values per image, weight 4-groups per class (zeros outside the image)
 template <int NB>
 struct HPLoad {
@@ -165,23 +184,7 @@ struct HPLoad {
 #pragma unroll
     for (int j = 0; j < 10; ++j) w[j] = hp_ld4(W + (int64_t)(j < NC ? j : 0) * 32 * QQ + rw.ldoff);
   }
-  // re-align the shifted edge groups, zero what lies outside the image and classes >= NC;
-  // wave-uniformly skipped for interior chunks with all classes present
-  __device__ __forceinline__ void fix(int NC) {
-    if (NC == 10 && __builtin_amdgcn_ballot_w64(sh != 0 || nvalid != 4) == 0) return;
-#pragma unroll
-    for (int j = 0; j < 10; ++j) {
-      const float e[4] = {w[j].x, w[j].y, w[j].z, w[j].w};
-      float o[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float v = e[k];
-        if (sh > 0) v = (k + sh < 4) ? e[(k + sh) & 3] : 0.f;
-        o[k] = (j < NC && k < nvalid) ? v : 0.f;
-      }
-      w[j] = make_float4(o[0], o[1], o[2], o[3]);
-    }
-  }
+  __device__ __forceinline__ void fix(int NC) { hp_fix_w(w, sh, nvalid, NC); }
 };
 
 // store a 4-group of class j of the weight layout at this thread's (row, 4 columns), inside the image only
@@ -733,6 +736,102 @@ __global__ __launch_bounds__(HP_THREADS) void head_upd_pb_kernel(const unsigned 
   }
 }
 
+// The shard form of head_upd_pb_kernel for the column-sharded exchange (parallel/factored.py, source
+// "pooled-sharded"): this rank owns the fc columns of channels [c0, c1) and holds every rank's ya
+// planes of those channels only, ya_sh [nranks][NB][c1-c0][plane] -- an image's stride is (c1-c0)
+// planes, not 32.  Same modes, same HPRow edge handling and the same arithmetic in the same order
+// (ranks ascending, then images; hp_fma4 / hp_relu / fmaf per element): bitwise the columns the full
+// kernel forms from the same inputs; nothing outside those columns is touched.
+// Shaped for few channels and many source images: at W = 8 the launch holds 4 channels, so the full
+// kernel's (channel, 2 block rows) grid would be 376 workgroups for 256 CUs.  Here a workgroup is one
+// (channel, block row, chunk of 32 blocks) -- 2256 at that shape -- and streams all nranks * NB
+// images past its 4 columns per thread; rank r+1's ya loads are issued before rank r's are consumed
+// (one look-ahead register set), so only rank 0's latency is exposed.  The weight is read in mode 0
+// only (the dW modes do not need it), issued first so it lands under the ya stream.
+template <int NB, int MODE>
+__global__ __launch_bounds__(HP_THREADS) void head_upd_pb_shard_kernel(const unsigned short* __restrict__ ya_sh,
+                                                                       const float* __restrict__ rec, int nranks,
+                                                                       const float* __restrict__ dl, const float* W,
+                                                                       float* out, PBGeom g, int NC, float scale,
+                                                                       float lr, int c0, int nc) {
+  const int nch = (g.Q8 + 31) / 32;
+  const int per_c = g.Q4 * nch;  // workgroups per channel
+  const int cl = (int)blockIdx.x / per_c, it = (int)blockIdx.x - cl * per_c;
+  const int c = c0 + cl, R = it / nch;
+  const HPThread th(it - R * nch);
+  const int Q = g.Q;
+  const int64_t plane = g.plane(), QQ = (int64_t)Q * Q;
+  const HPRow rw(g, th, c, R);
+  float4 w[10];
+  if constexpr (MODE == 0) {
+#pragma unroll
+    for (int j = 0; j < 10; ++j) w[j] = hp_ld4(W + (int64_t)(j < NC ? j : 0) * 32 * QQ + rw.ldoff);
+  }
+  const int py = 4 * R + th.prow, px0 = th.blk * 8 + th.half * 4;
+  const bool rok = th.blk < g.Q8 && py < Q;
+  // this thread's 4 values inside plane (r, b, cl); idle lanes of the last chunk read a valid block
+  const int64_t yi = (int64_t)cl * plane + ((int64_t)R * g.Q8 + (th.blk < g.Q8 ? th.blk : g.Q8 - 1)) * 32 + th.part * 4;
+  const int64_t y_bs = (int64_t)nc * plane;  // image stride
+  float acc[10][4];
+#pragma unroll
+  for (int j = 0; j < 10; ++j)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[j][k] = 0.f;
+  uint2 yn[NB];  // the look-ahead set
+#pragma unroll
+  for (int b = 0; b < NB; ++b) yn[b] = *reinterpret_cast<const uint2*>(ya_sh + (int64_t)b * y_bs + yi);
+#pragma unroll 1
+  for (int r = 0; r < nranks; ++r) {
+    uint2 y[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) y[b] = yn[b];
+    if (r + 1 < nranks) {
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+        yn[b] = *reinterpret_cast<const uint2*>(ya_sh + ((int64_t)(r + 1) * NB + b) * y_bs + yi);
+    }
+    // rank r's head constants, formed as its head kernels formed them (head_fwd_pb_kernel)
+    const float* rr = rec + (int64_t)r * HP_REC;
+    const TdsYaDec yd{rr + 68, reinterpret_cast<const uint32_t*>(rr + 64)};
+    const float a = rr[c], ad = a * hp_ydec(yd.ysc), bd = fmaf(a, yd.b2[c], rr[32 + c]);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      float zz[4];
+      hp_fma4(ad, y[b], bd, zz);
+      float x[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) x[k] = (rok && px0 + k < Q) ? hp_relu(zz[k]) : 0.f;
+#pragma unroll
+      for (int j = 0; j < 10; ++j) {
+        if (j < NC) {
+          const float dv = dl[(r * NB + b) * NC + j];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) acc[j][k] = fmaf(dv, x[k], acc[j][k]);
+        }
+      }
+    }
+  }
+  if constexpr (MODE == 0) hp_fix_w(w, rw.sh, rw.nvalid, NC);
+#pragma unroll
+  for (int j = 0; j < 10; ++j) {
+    if (j < NC) {
+      const float4 d = make_float4(scale * acc[j][0], scale * acc[j][1], scale * acc[j][2], scale * acc[j][3]);
+      if constexpr (MODE == 0) {
+        const float4 wj = w[j];
+        hp_store4(out, g, rw, j, make_float4(wj.x - lr * d.x, wj.y - lr * d.y, wj.z - lr * d.z, wj.w - lr * d.w));
+      } else if constexpr (MODE == 1) {
+        hp_store4(out, g, rw, j, d);
+      } else if (rw.nvalid > 0) {
+        float* p = out + (int64_t)j * 32 * QQ + rw.off;
+        const float e[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (k < rw.nvalid) p[k] += e[k];
+      }
+    }
+  }
+}
+
 // one rank's record (HP_REC floats): aff2 [64] | the ya scale words [3] (1, 1, 1 without) | 0 | b2 [32] | 0
 __global__ __launch_bounds__(HP_REC) void hp_record_kernel(const float* __restrict__ aff2, const float* __restrict__ b2,
                                                           const uint32_t* __restrict__ ysc, float* __restrict__ rec) {
@@ -777,6 +876,37 @@ int tds_head_upd_pb(const unsigned short* ya_all, int64_t ya_rs, const float* re
   }
 #undef TDS_HPU
 #undef TDS_HPU_M
+  TDS_LAUNCH_CHECK();
+  return 0;
+}
+
+int tds_head_upd_pb_shard(const unsigned short* ya_sh, const float* rec, int nranks, const float* dl, const float* W,
+                          float* out, int B, int Q, int NC, int c0, int c1, float scale, float lr, int mode,
+                          hipStream_t st) {
+  if (B < 1 || B > HP_MAXB || NC < 1 || NC > 10 || Q < 4 || nranks < 1 || mode < 0 || mode > 2) return -1;
+  if (c0 < 0 || c1 > 32 || c0 >= c1) return -1;
+  const PBGeom g = pb_geom(Q);
+  const int nc = c1 - c0;
+  const int nwg = nc * g.Q4 * ((g.Q8 + 31) / 32);
+#define TDS_HPS_M(NBV, MD)                                                                                        \
+  hipLaunchKernelGGL((head_upd_pb_shard_kernel<NBV, MD>), dim3(nwg), dim3(HP_THREADS), 0, st, ya_sh, rec, nranks, \
+                     dl, W, out, g, NC, scale, lr, c0, nc);
+#define TDS_HPS(NBV)                                    \
+  case NBV:                                             \
+    if (mode == 0) {                                    \
+      TDS_HPS_M(NBV, 0)                                 \
+    } else if (mode == 1) {                             \
+      TDS_HPS_M(NBV, 1)                                 \
+    } else {                                            \
+      TDS_HPS_M(NBV, 2)                                 \
+    }                                                   \
+    break;
+  switch (B) {
+    TDS_HPS(1) TDS_HPS(2) TDS_HPS(3) TDS_HPS(4) TDS_HPS(5) TDS_HPS(6) TDS_HPS(7) TDS_HPS(8)
+    default: return -1;
+  }
+#undef TDS_HPS
+#undef TDS_HPS_M
   TDS_LAUNCH_CHECK();
   return 0;
 }

@@ -214,6 +214,13 @@ int tds_head_bwd_pb_npass(int B);
 // 2: out += scale * dl^T X
 int tds_head_upd_pb(const unsigned short* ya_all, int64_t ya_rs, const float* rec, int nranks, const float* dl,
                     const float* W, float* out, int B, int Q, int NC, float scale, float lr, int mode, hipStream_t st);
+// The shard form (the column-sharded exchange from the pooled input): the columns of channels [c0, c1)
+// only, from ya_sh [nranks][B][c1-c0][PB] fp16 (every rank's planes of those channels); W and out
+// stay full width, nothing outside those columns is read or written.  Bitwise the columns
+// tds_head_upd_pb forms from the same inputs.
+int tds_head_upd_pb_shard(const unsigned short* ya_sh, const float* rec, int nranks, const float* dl, const float* W,
+                          float* out, int B, int Q, int NC, int c0, int c1, float scale, float lr, int mode,
+                          hipStream_t st);
 // a rank's record for tds_head_upd_pb: aff2 [64] | ya scale words [3] (ysc nullptr: 1, 1, 1) | 0 | b2 [32] | 0
 void tds_head_pooled_record(const float* aff2, const float* b2, const uint32_t* ysc, float* rec, hipStream_t st);
 // channels [c0, c1) only (K-chunked fc gradient: each chunk's dW columns can be all-reduced as

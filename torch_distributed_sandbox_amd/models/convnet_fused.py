@@ -228,7 +228,7 @@ class _Layer2Link:
         self.mag = None
         self.labels = None  # the batch's labels (attach_labels) -> ce = (labels, loss, dlogits) from the head
         self.ce = None
-        self.pooled = False  # the activation exchange started from the pooled input (forward below)
+        self.pooled = False  # the fc exchange started from the pooled input (forward below)
 
 
 # The small reductions behind BN2 (forward statistics, backward constants) and the logits run
@@ -473,7 +473,9 @@ def forward(model, x):
                                       link, link1)
     # the activation exchange from the pooled input (parallel/factored.py "pooled"): ya and this
     # rank's head constants leave right here, after the conv2 forward and before the previous step's
-    # deferred fc update and the head forward, which then write no fc input rows
+    # deferred fc update and the head forward, which then write no fc input rows.  ex.pooled(B) also
+    # agrees for the sharded path under source "pooled-sharded": ya's channel planes go to their
+    # owners from here, and the head forward allocates no x_out and calls no ex.begin
     ex = factored.get(fc.weight)
     B = x.shape[0]
     if ex is not None and link.bn_done and B <= 8 and ex.ready(B) and ex.pooled(B):

@@ -41,6 +41,7 @@ from __future__ import annotations
 
 import contextlib
 import hashlib
+import os
 import weakref
 from typing import List, Optional
 
@@ -128,6 +129,16 @@ class DistributedDataParallel(nn.Module):
         if grad_exchange not in ("auto", "allreduce", "activations", "sharded", "chunked"):
             raise ValueError(f"grad_exchange must be auto|allreduce|activations|sharded|chunked, got {grad_exchange!r}")
         self.grad_exchange = grad_exchange
+        # the exchange's source (parallel/factored.py: pooled | rows | pooled-sharded).  A non-empty
+        # TDS_EXCHANGE_SOURCE overrides the argument: the operator's switch (like
+        # TDS_EXCHANGE_UPDATE), so a launcher that does not offer a value can still run it
+        env_source = os.environ.get("TDS_EXCHANGE_SOURCE", "").strip()
+        if env_source:
+            exchange_source = env_source
+        if exchange_source not in factored.EXCHANGE_SOURCES:
+            raise ValueError(
+                f"exchange_source must be {'|'.join(factored.EXCHANGE_SOURCES)}, got {exchange_source!r}")
+        self.exchange_source = exchange_source
         # K-chunked all-reduce of a big layer's weight gradient (parallel/factored.py, "chunked"):
         # default 4 chunks on the GPU, off on the CPU
         if allreduce_chunks is None:
@@ -238,7 +249,8 @@ class DistributedDataParallel(nn.Module):
                     # a group's head launch in (earlier window) for ~0.2 ms of launch and tail cost at
                     # the bench shape, worth it only when links carry the rows (world > 1)
                     groups=exchange_groups if exchange_groups else (4 if self.world_size > 1 else 1),
-                    # the fused head's pooled input instead of the fc rows X (factored.py "pooled")
+                    # the fused head's pooled input instead of the fc rows X (factored.py "pooled";
+                    # "pooled-sharded": on the sharded path too)
                     source=exchange_source))
 
         # ---- overlapped optimizer: the big layers' buckets finish (collective + SGD
@@ -641,7 +653,8 @@ class DistributedDataParallel(nn.Module):
     # (leftovers of the deferred buckets at most this many elements, with no collective behind them,
     # are updated inline by the optimizer's own sweep: at world size 1 the fc weight's step runs in
     # its backward kernel and only the fc bias is left -- on the side stream it cost the next head
-    # forward a cross-stream wait, an ~11 us gap in the step's timeline, r5_s36)
+    # forward a cross-stream wait, an ~11 us gap in the step's timeline, r5_s36).  Not when an exchange
+    # forced at world size 1 left unjoined work on the side stream this step: see take_inline_deferred
     _INLINE_DEFERRED_MAX = 1 << 16
 
     def take_inline_deferred(self):
@@ -649,7 +662,14 @@ class DistributedDataParallel(nn.Module):
         own sweep on the current stream this step (see _INLINE_DEFERRED_MAX); they are skipped by
         _run_deferred_update, which then fences only what it updates itself."""
         self._inline_done = set()
-        if self.world_size != 1 or not self._deferred:
+        # an exchange forced at world size 1 finished on the side stream (the fc weight updated in place
+        # there, the bias gradient written there) and nothing joined it: no inline step of the bias on
+        # this stream and no fast path -- the side-stream update below follows that work in stream
+        # order and fences the weight and the bias for the next forward
+        side_pending = [ex for ex in self._exchanges if ex.side_pending]
+        for ex in side_pending:
+            ex.side_pending = False
+        if self.world_size != 1 or not self._deferred or side_pending:
             return []
         left = [p for b in self._deferred for p in b.params if id(p) not in self._fused_done]
         if not left or sum(p.numel() for p in left) > self._INLINE_DEFERRED_MAX:

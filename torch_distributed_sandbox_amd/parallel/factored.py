@@ -62,6 +62,18 @@ rank forms the fc step from them (``ops.head_update_pooled``), recomputing each 
 rank's constants and the head forward's own arithmetic: bitwise the rows the dense exchange would
 have sent.  ``link_bytes`` prices it at x_ratio 0.5.
 
+Pooled sharded source (``source="pooled-sharded"``, opt-in): the sharded path from the same pooled
+input.  The fc weight's columns are ordered (channel, row, column) and a (image, channel) plane of
+ya is one contiguous run, so a shard of whole channels (``plane_shards``) is contiguous on both
+sides and nothing is encoded: each rank all-gathers its 128 head constants and sends owner s the
+planes ``ya[b, c0_s:c1_s]`` of its B images in one grouped exchange -- no encode, no count gather,
+no host check.  The owner forms its channels' columns from every rank's planes
+(``ops.head_update_pooled_shard``: the arithmetic of ``head_update_pooled`` in the same order, so
+the columns are bitwise those of the pooled activation path) and the shards are all-gathered as on
+the rows path.  The activation path under this source is the pooled one above.  Not offered at
+world > 1 under DDP's overlapped optimizer (``_pooled_sharded_ok``): the sharded path then stays on
+the rows.
+
 Column groups (activation path, zero-suppressed): the rows travel as ``groups`` column ranges
 (whole channel planes on the fused head), each encoded and gathered on its own.  The fused head
 forward runs one launch per group and hands each group's rows over as soon as its launch is
@@ -153,6 +165,19 @@ def shard_bounds(in_f: int, world: int) -> List[Tuple[int, int]]:
     return [(min(in_f, r * per), min(in_f, (r + 1) * per)) for r in range(world)]
 
 
+def plane_shards(world: int, planes: int = 32) -> List[Tuple[int, int]]:
+    """The [c0, c1) channel ranges of the pooled sharded exchange, one per rank: cuts at
+    round(i * planes / world) (the rule of ``column_chunks``), so shards differ by at most one
+    plane and every rank computes the same ones.  Ranks past ``planes`` would own nothing: the
+    exchange takes this form only for world <= planes."""
+    cuts = [round(i * planes / world) for i in range(world + 1)]
+    return [(cuts[i], cuts[i + 1]) for i in range(world)]
+
+
+# what an exchange sends (ActivationExchange ``source``, DDP ``exchange_source``, --exchange-source)
+EXCHANGE_SOURCES = ("pooled", "rows", "pooled-sharded")
+
+
 class ActivationExchange:
     """One exchange-capable Linear layer under DDP (see the module docstring)."""
 
@@ -168,10 +193,11 @@ class ActivationExchange:
         self.group, self.world, self.mode = group, world, mode
         self.chunks = max(1, int(chunks))
         self.groups = max(1, int(groups))  # column groups of the zero-suppressed activation path
-        if source not in ("pooled", "rows"):
-            raise ValueError(f"ActivationExchange source must be pooled|rows, got {source!r}")
+        if source not in EXCHANGE_SOURCES:
+            raise ValueError(f"ActivationExchange source must be {'|'.join(EXCHANGE_SOURCES)}, got {source!r}")
         # "pooled": the activation path takes the fused head's pooled input when the layer offers
-        # it (begin_pooled); "rows": always the fc input rows X (begin / begin_groups)
+        # it (begin_pooled); "rows": always the fc input rows X (begin / begin_groups);
+        # "pooled-sharded": as "pooled", and the sharded path takes the pooled input too
         self.source = source
         self._pooled = None  # this step's pooled exchange (dict), or None
         self._works = []  # chunked: the per-chunk all-reduce works of this step
@@ -182,6 +208,9 @@ class ActivationExchange:
         self.last_path = None  # "activation-exchange" | "sharded-exchange" once a step used it
         self._x_buf = self._x_work = self._dy = self._x_local = None
         self.side_stream = None  # DDP(overlap_optimizer=True): its update stream, which also finishes the exchange
+        # this step left work on DDP's side stream that nothing joined (the finish, or the bias gradient of
+        # the deferred update): DDP fences the layer's parameters behind it (ddp.py take_inline_deferred)
+        self.side_pending = False
         self._own_stream = None  # otherwise (GPU): a private side stream
         # zero-suppressed activation rows (parallel/zs.py)
         self.compress = bool(compress)
@@ -330,13 +359,13 @@ class ActivationExchange:
             nb = dst.numel() * dst.element_size()
             timed(name, nb, "all_gather", lambda: tdist.all_gather_into_tensor(dst, src, group=g, async_op=True))
 
-        def peers(name, numel, nrows):
+        def peers(name, numel, nrows, dtype=torch.float32):
             # one grouped exchange with every peer: nrows chunks of numel elements each way
-            bufs_s = [torch.zeros(numel, device=dev) for _ in range(nrows)]
-            bufs_r = [torch.empty(numel, device=dev) for _ in range(nrows * W)]
+            bufs_s = [torch.zeros(numel, device=dev, dtype=dtype) for _ in range(nrows)]
+            bufs_r = [torch.empty(numel, device=dev, dtype=dtype) for _ in range(nrows * W)]
             sends = [(t, p) for p in range(W) if p != me for t in bufs_s]
             recvs = [(bufs_r[p * nrows + i], p) for p in range(W) if p != me for i in range(nrows)]
-            nb = numel * 4 * nrows  # per peer (link)
+            nb = numel * bufs_s[0].element_size() * nrows  # per peer (link)
             timed(name, nb, "sendrecv", lambda: tdist.sendrecv(sends, recvs, group=g, async_op=True))
 
         n = rows * in_f
@@ -359,6 +388,12 @@ class ActivationExchange:
             else:
                 gather("activation rows all-gather", n, torch.float32)
             gather("dY all-gather", rows * out_f, torch.float32)
+        elif path == "sharded" and pb is not None and self._pooled_sharded_ok():
+            widest = max(e - a for a, e in plane_shards(W))  # channels of the largest shard
+            gather("head record all-gather", 128, torch.float32)
+            peers("pooled input (ya) channel-shard exchange (per peer)", widest * pb, rows, torch.float16)
+            gather("dY all-gather", rows * out_f, torch.float32)
+            peers("updated W shard exchange (per peer)", widest * (in_f // 32), out_f)
         elif path == "sharded":
             longest = max(e - a for a, e in shard_bounds(in_f, W))
             if zs_ok:
@@ -442,24 +477,44 @@ class ActivationExchange:
         return self.compress and self._eligible(rows) == "activations" and rows * in_f < (1 << 31)
 
     def pooled_capable(self) -> bool:
-        """Can this layer's activation exchange run from the pooled input (source "pooled", a GPU
-        weight whose inputs are the fused head's 32 square planes)?  The byte model and the preflight
-        price it so; the fused ConvNet head then takes it (a generic Linear still sends its rows)."""
-        return self.source == "pooled" and self.weight.is_cuda and pooled_plane(self.weight.shape[1]) is not None
+        """Can this layer's activation exchange run from the pooled input (source "pooled" or
+        "pooled-sharded", a GPU weight whose inputs are the fused head's 32 square planes)?  The byte
+        model and the preflight price it so; the fused ConvNet head then takes it (a generic Linear
+        still sends its rows)."""
+        return (self.source in ("pooled", "pooled-sharded") and self.weight.is_cuda
+                and pooled_plane(self.weight.shape[1]) is not None)
+
+    def _pooled_sharded_ok(self) -> bool:
+        """Does the sharded path run from the pooled input?  Every rank must own at least one of
+        the 32 channel planes.  Under DDP's overlapped optimizer at world > 1 (``side_stream`` set:
+        the finish runs unjoined on DDP's stream, update-only with the fused step) the sharded path
+        stays on the rows: the multi-rank test of that combination failed once on an MI355X for a
+        reason that was never found, so that combination is not offered (docs/DISTRIBUTED.md
+        "Pooled sharded source")."""
+        if self.world > 1 and self.side_stream is not None:
+            return False
+        return self.source == "pooled-sharded" and self.pooled_capable() and self.world <= 32
 
     def pooled(self, rows: int) -> bool:
-        """Would a forward with ``rows`` rows run the activation exchange from the pooled input
-        (``begin_pooled``)?"""
-        return self.source == "pooled" and self._eligible(rows) == "activations"
+        """Would a forward with ``rows`` rows run its exchange from the pooled input
+        (``begin_pooled``): the activation path, or the sharded path under "pooled-sharded"?"""
+        path = self._eligible(rows)
+        if path == "activations":
+            return self.source in ("pooled", "pooled-sharded")
+        return path == "sharded" and self._pooled_sharded_ok()
 
     def begin_pooled(self, ya: torch.Tensor, rec: torch.Tensor, P: int) -> None:
-        """Start the activation exchange from the fused head's pooled input (module docstring): the
-        all-gathers of this rank's head record (128 floats, ``ops.head_pooled_record``) and of ya
-        ([rows, 32, PB] fp16), queued where the conv2 forward wrote ya, before the head forward."""
+        """Start the exchange from the fused head's pooled input (module docstring), queued where
+        the conv2 forward wrote ya, before the head forward.  Activation path: the all-gathers of
+        this rank's head record (128 floats, ``ops.head_pooled_record``) and of ya ([rows, 32, PB]
+        fp16); sharded path (``pooled`` agreed to it): ``_begin_pooled_sharded``."""
         from . import distributed as tdist
 
         ya = ya.detach().contiguous()
         rec = rec.detach().contiguous().view(-1)
+        if self._eligible(ya.shape[0]) == "sharded":
+            self._begin_pooled_sharded(ya, rec, P)
+            return
         W = self.world
         rec_all = torch.empty((W, rec.numel()), device=rec.device, dtype=rec.dtype)
         w_rec = tdist.all_gather_into_tensor(rec_all.view(-1), rec, group=self.group, async_op=True)
@@ -467,14 +522,40 @@ class ActivationExchange:
         w_ya = tdist.all_gather_into_tensor(ya_all.view(-1), ya.view(-1), group=self.group, async_op=True)
         self._pooled = {"ya_all": ya_all, "rec_all": rec_all, "w_ya": w_ya, "w_rec": w_rec, "P": int(P),
                         "keep": (ya, rec)}
+        self._pooled_started(ya, rec, "activations")
+
+    def _pooled_started(self, ya, rec, path: str):
         self._zs = None
         self._step_zs = False
         self._x_local = ya  # keep alive until the exchange completes
         self._x_work = None
         out_f, in_f = self.weight.shape
+        # (bytes sent relative to the dense fp32 rows; the sharded path sends each plane to one owner)
         self.x_ratio = (ya.numel() * ya.element_size() + rec.numel() * 4) / float(ya.shape[0] * in_f * 4)
-        self.active = "activations"
+        self.active = path
         self._set_skip(True)
+
+    def _begin_pooled_sharded(self, ya: torch.Tensor, rec: torch.Tensor, P: int) -> None:
+        """The sharded exchange from the pooled input: all-gather the head records, and one grouped
+        exchange that sends owner s this rank's planes ``ya[b, c0_s:c1_s]`` (contiguous, fp16) of
+        every image b and receives every rank's planes of this rank's channels into
+        ya_sh [W, B, nc_me, PB].  Nothing is encoded or counted."""
+        from . import distributed as tdist
+
+        W = self.world
+        me = tdist.get_rank(self.group)
+        B, planes, pb = ya.shape
+        shards = plane_shards(W, planes)
+        c0, c1 = shards[me]
+        rec_all = torch.empty((W, rec.numel()), device=rec.device, dtype=rec.dtype)
+        w_rec = tdist.all_gather_into_tensor(rec_all.view(-1), rec, group=self.group, async_op=True)
+        ya_sh = torch.empty((W, B, c1 - c0, pb), device=ya.device, dtype=ya.dtype)
+        sends = [(ya[b, a:e].view(-1), s) for s, (a, e) in enumerate(shards) for b in range(B)]
+        recvs = [(ya_sh[s, b].view(-1), s) for s in range(W) for b in range(B)]
+        w_ya = tdist.sendrecv(sends, recvs, group=self.group, async_op=True)
+        self._pooled = {"ya_all": ya_sh, "rec_all": rec_all, "w_ya": w_ya, "w_rec": w_rec, "P": int(P),
+                        "keep": (ya, rec), "shards": shards}
+        self._pooled_started(ya, rec, "sharded")
 
     def _pooled_update(self, p, dy_all, out, scale: float, lr: float, acc: bool = False):
         """The fc step from the gathered pooled inputs on the current stream, after both gathers:
@@ -885,6 +966,8 @@ class ActivationExchange:
             self._finish()
         if join:
             cur.wait_stream(side)
+        else:
+            self.side_pending = True
 
     def _defer_update_inline(self) -> bool:
         """Activations path under DDP's overlapped optimizer with the step fused in (plain SGD):
@@ -929,6 +1012,7 @@ class ActivationExchange:
                 self.bias.grad = db
             ev_dy = torch.cuda.Event()
             ev_dy.record(side)
+        self.side_pending = True  # (db was written on the side stream)
         z, self._zs = self._zs, None
         pooled, self._pooled = self._pooled, None
         x_work, x_dense = self._x_work, self._x_buf
@@ -1101,6 +1185,9 @@ class ActivationExchange:
         the bucket slot (accumulated under no_sync as ``_targets`` sets up) and db."""
         from ..ops import fused_update
 
+        if "shards" in pooled:
+            self._finish_pooled_sharded(pooled, dy_all)
+            return
         scale = 1.0 / self.world
         lr = fused_update.take(self.weight, exchanged=True)
         with torch.no_grad():
@@ -1114,6 +1201,51 @@ class ActivationExchange:
             if db is not None:
                 s_b = dy_all.sum(0).mul_(scale)
                 db.add_(s_b) if acc_b else db.copy_(s_b)
+        if self.bias is not None:
+            self.bias.grad = db
+        if lr:
+            fused_update.applied(self.weight)
+        self._pooled_tag = True
+        self._done()
+
+    def _finish_pooled_sharded(self, pooled, dy_all):
+        """``_finish`` of a pooled sharded step, with the rows path's placement: this rank forms
+        the columns of its channels from every rank's planes -- the update-only step writes the
+        UPDATED weight shard in place, otherwise dW's shard goes into the bucket slot (accumulated
+        under no_sync as ``_targets`` sets up) -- and the shards are all-gathered by one grouped
+        exchange straight into W / dW; db from dy_all."""
+        from .. import _ext
+        from ..ops import fused_update
+        from . import distributed as tdist
+
+        W, scale = self.world, 1.0 / self.world
+        me = tdist.get_rank(self.group)
+        shards = pooled["shards"]
+        c0, c1 = shards[me]
+        n_out, in_f = self.weight.shape
+        per = in_f // 32  # columns per channel
+        lr = fused_update.take(self.weight, exchanged=True)
+        pooled["w_rec"].wait()
+        pooled["w_ya"].wait()
+        with torch.no_grad():
+            if lr:
+                (_, _), (db, acc_b) = self._targets(weight=False)
+                tgt, out, mode = self.weight.data, None, 0
+            else:
+                (dw, acc_w), (db, acc_b) = self._targets()
+                tgt, out, mode = dw, dw, 2 if acc_w else 1
+            _ext.ops().head_update_pooled_shard(dy_all, pooled["ya_all"], pooled["rec_all"], self.weight.data, out,
+                                                pooled["P"], c0, c1, scale, float(lr or 0.0), mode)
+            k0, k1 = c0 * per, c1 * per
+            sends = [(tgt[j, k0:k1], s) for s in range(W) if s != me for j in range(n_out)]
+            recvs = [(tgt[j, a * per:e * per], s) for s, (a, e) in enumerate(shards) if s != me for j in range(n_out)]
+            if sends or recvs:
+                tdist.sendrecv(sends, recvs, group=self.group, async_op=True).wait()
+            if db is not None:
+                s_b = dy_all.sum(0).mul_(scale)
+                db.add_(s_b) if acc_b else db.copy_(s_b)
+        if not lr:
+            self.weight.grad = dw
         if self.bias is not None:
             self.bias.grad = db
         if lr:

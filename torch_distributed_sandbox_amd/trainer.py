@@ -26,6 +26,7 @@ from .ops import CrossEntropyLoss, SGD
 from .ops import functional as TF
 from .parallel import DistributedDataParallel, DistributedSampler
 from .parallel import distributed as tdist
+from .parallel.factored import EXCHANGE_SOURCES
 from .utils import checkpoint, fault
 from .utils.timing import StepTimer
 
@@ -48,6 +49,9 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--json", action="store_true", help="print a JSON summary line at the end")
     p.add_argument("--grad-exchange", default="auto", choices=["auto", "allreduce", "activations", "sharded", "chunked"],
                    help="DDP gradient path of the big fc layer (parallel/factored.py)")
+    p.add_argument("--exchange-source", default="pooled", choices=list(EXCHANGE_SOURCES),
+                   help="what the fc exchange sends: the fused head's pooled input (activation path), the fc input "
+                        "rows, or the pooled input on the sharded path too (parallel/factored.py)")
     p.add_argument("--phase-times", action="store_true",
                    help="time forward / backward / optimizer per step with HIP events (utils/timing.StepTimer; "
                         "adds them to the summary; roctx ranges with TDS_ROCTX=1)")
@@ -109,6 +113,7 @@ def train(gpu: int, args, distributed: bool = False) -> dict:
         model = DistributedDataParallel(model, device_ids=[gpu] if device.type == "cuda" else None,
                                         bucket_cap_mb=getattr(args, "bucket_mb", None),
                                         grad_exchange=getattr(args, "grad_exchange", "auto"),
+                                        exchange_source=getattr(args, "exchange_source", "pooled"),
                                         overlap_optimizer=getattr(args, "overlap_optimizer", True))
         model.attach_optimizer(optimizer)
     start_epoch = 0
