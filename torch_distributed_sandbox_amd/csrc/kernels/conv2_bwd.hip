@@ -83,14 +83,15 @@ struct BRTile {
   int b, r0, c0;
   bool start, end;
 };
-__device__ __forceinline__ BRTile br_decode(const int* __restrict__ walk, int k, int sk, int w) {
+__device__ __forceinline__ uint32_t br_entry(const int* __restrict__ walk, int k, int sk) {
   // 32-bit index (the table is far below 2^31 entries): with a 64-bit one the compiler keeps
   // copies of the wgrad accumulators across the tile loop and spills them (256 VGPRs + scratch
   // against 189).  walk is already offset to this workgroup's list (w * sw); the device table is
   // per workgroup ([nwg][rows], fused_ops.cpp bwd_walk, sk = 1): 16 consecutive tiles per
   // scalar-cache line.
-  (void)w;
-  const uint32_t v = (uint32_t)walk[k * sk];
+  return (uint32_t)walk[k * sk];
+}
+__device__ __forceinline__ BRTile br_tile(uint32_t v) {
   BRTile x;
   x.start = (v & kWalkStart) != 0;
   x.end = (v & kWalkEnd) != 0;
@@ -98,6 +99,22 @@ __device__ __forceinline__ BRTile br_decode(const int* __restrict__ walk, int k,
   x.r0 = (int)((v >> 12) & 4095) * BR_TH;
   x.c0 = (int)(v & 4095) * BR_TC;
   return x;
+}
+__device__ __forceinline__ BRTile br_decode(const int* __restrict__ walk, int k, int sk, int w) {
+  (void)w;
+  return br_tile(br_entry(walk, k, sk));
+}
+
+// tiles of a list: its first end entry, by bisection (entry rows - BR_WALK_PAD is an end entry in
+// every list: tds_conv2_bwd_walk pads the longest one with that many)
+__device__ __forceinline__ int br_count(const int* __restrict__ walk, int sk, int rows) {
+  int lo = 0, hi = rows - BR_WALK_PAD;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (br_entry(walk, mid, sk) & kWalkEnd) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
 }
 
 struct BRArgs {
@@ -108,7 +125,7 @@ struct BRArgs {
   uint2* __restrict__ dp1;  // dp1h (conv2_common.h)
   float* __restrict__ slab;
   const int* __restrict__ walk;
-  int B, P, Q, sk, w;
+  int B, P, Q, sk, w, rows;  // rows: entries per list (its tiles, then >= BR_WALK_PAD end entries)
 };
 
 // ---------------------------------------------------------------------------- dgrad
@@ -331,11 +348,25 @@ __device__ __forceinline__ void br_mfma(const BRArgs& a, const uint4* __restrict
   BRTile prev{0, 0, 0, false, true};
   BRClock<DIAG> clk;
   clk.start();
+  // No scalar load is waited for at a tile boundary (the matrix pipe drains meanwhile): the wgrad
+  // waves need only the list's length and count it once; the dgrad waves fetch tile kk + 1's entry
+  // BEFORE the barrier of tile kk, whose lgkmcnt(0) they wait out anyway.
+  const int ntiles = ROLE >= 2 ? br_count(a.walk, a.sk, a.rows) : 0;
+  uint32_t nxt = ROLE < 2 ? br_entry(a.walk, 0, a.sk) : 0u;
   int kk = 0;
   for (;; ++kk) {
-    const BRTile cur = br_decode(a.walk, kk, a.sk, a.w);
-    if (cur.end) break;
+    BRTile cur{0, 0, 0, false, false};
+    if constexpr (ROLE >= 2) {
+      if (kk >= ntiles) break;
+    } else {
+      cur = br_tile(nxt);
+      if (cur.end) break;
+      nxt = br_entry(a.walk, kk + 1, a.sk);
+    }
     clk.barrier();  // tile kk staged; the partner's exchange slot of tile kk-1 is written
+    // (the entry has arrived with the barrier's own wait: consumed here, so that no operand read
+    // of the tile below is waited for together with it)
+    if constexpr (ROLE < 2) asm volatile("" ::"s"(nxt));
     const BRRows rw = br_rows(smem, kk);
     if constexpr (br_idle(DIAG, ROLE)) {
       // timing-only: this role does nothing but the barriers
@@ -444,56 +475,61 @@ struct BRStager {
     return R0 >= 0 && R0 + NR <= 2 * a.Q && c0 - 2 >= 0 && c0 + BR_TC + 2 <= 2 * a.Q;
   }
 
-  // (bounds as bitwise &, | of unsigned compares: short-circuit && / || compiled to exec-mask
-  // branches around every load's address, and the merges cost a vmcnt(0) per load set)
-  __device__ __forceinline__ void load(const BRArgs& a, int b, int R0, int c0, int tid) {
-    if constexpr (br_no_gload(DIAG)) {
-#pragma unroll
-      for (int u = 0; u < IPER; ++u) {
-#pragma unroll
-        for (int k = 0; k < BR_CW; ++k) gv[u][k] = 0.f;
-        av[u] = 0u;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) yv[u][q] = BRY{};
-      }
-#pragma unroll
-      for (int j = 0; j < PPER; ++j) pr[j] = make_uint4(0u, 0u, 0u, 0u);
-      return;
-    }
+  // The addresses of a block's loads in two parts.  Bases: the byte address of each of the four
+  // descriptors' origin -- y2h / p1 at (R0, c0-2), g2m / a2 at the pooled (R0/2, c0/2-1) of image b
+  // -- wave-uniform, SALU.  The next tile down a segment (R0 + 8) moves them by constants (Steps),
+  // so the pipelined sets carry them from tile to tile (br_stage) instead of rebuilding them
+  // (64-bit multiplies and add chains, ~100 SALU a tile).
+  struct Bases {
+    uint64_t y, p, g, a;
+  };
+  __device__ __forceinline__ static Bases bases(const BRArgs& a, int b, int R0, int c0) {
     const int P = a.P, Q = a.Q;
-    const bool in = interior(a, R0, c0);
     const int64_t img = (int64_t)b * P;
-    // y2 / p1: one descriptor per block, based at (R0, c0-2); lanes outside the image -> kBROob
-    const __amdgpu_buffer_rsrc_t ry =
-        tds_buffer_rsrc(reinterpret_cast<const char*>(a.y2) + ((img + R0) * P + (c0 - 2)) * 64, 0xFFFFFFF0u);
-    const __amdgpu_buffer_rsrc_t rp =
-        tds_buffer_rsrc(reinterpret_cast<const char*>(a.p1) + ((img + R0) * P + (c0 - 2)) * 32, 0xFFFFFFF0u);
     const int64_t gplane = (int64_t)Q * Q;
     const int py0 = R0 / 2, px0 = c0 / 2 - 1;
-    const __amdgpu_buffer_rsrc_t rg =
-        tds_buffer_rsrc(a.g2m + (int64_t)b * 32 * gplane + (int64_t)py0 * Q + px0, 0xFFFFFFF0u);
-    const __amdgpu_buffer_rsrc_t ra = tds_buffer_rsrc(a.a2 + (((int64_t)b * Q + py0) * Q + px0) * 2, 0xFFFFFFF0u);
+    Bases x;
+    x.y = reinterpret_cast<uint64_t>(reinterpret_cast<const char*>(a.y2) + ((img + R0) * P + (c0 - 2)) * 64);
+    x.p = reinterpret_cast<uint64_t>(reinterpret_cast<const char*>(a.p1) + ((img + R0) * P + (c0 - 2)) * 32);
+    x.g = reinterpret_cast<uint64_t>(a.g2m + (int64_t)b * 32 * gplane + (int64_t)py0 * Q + px0);
+    x.a = reinterpret_cast<uint64_t>(a.a2 + (((int64_t)b * Q + py0) * Q + px0) * 2);
+    return x;
+  }
+  // bytes the bases move by from a tile to the next one of its segment (8 image rows = 4 pooled rows)
+  struct Steps {
+    uint32_t y, p, g, a;
+  };
+  __device__ __forceinline__ static Steps steps(const BRArgs& a) {
+    return Steps{(uint32_t)(8 * a.P * 64), (uint32_t)(8 * a.P * 32), (uint32_t)(4 * a.Q * 2), (uint32_t)(4 * a.Q * 8)};
+  }
+  __device__ __forceinline__ static Bases next_down(const Bases& x, const Steps& d) {
+    return Bases{x.y + d.y, x.p + d.p, x.g + d.g, x.a + d.a};
+  }
+
+  // Offs: each lane's byte offsets from those bases (kBROob: the lane loads zeros).  With in (an
+  // interior block: interior()) they depend on the lane alone -- the pipelined sets compute them
+  // once before the tile loop and only a border block selects per lane by its bounds.
+  // (bounds as bitwise &, | of unsigned compares: short-circuit && / || compiled to exec-mask
+  // branches around every load's address, and the merges cost a vmcnt(0) per load set)
+  struct Offs {
+    uint32_t y[IPER][4], a[IPER], p[PPER];
+    uint32_t gl, gm, gr;  // GB: the run's left halo column, its 8 inner columns, the right halo
+  };
+  __device__ __forceinline__ static Offs offsets(const BRArgs& a, int R0, int c0, int tid, bool in) {
+    const int P = a.P, Q = a.Q;
+    const int py0 = R0 / 2, px0 = c0 / 2 - 1;
+    Offs o;
+    o.gl = o.gm = o.gr = kBROob;
     if constexpr (GB) {
-      // the runs first: put_runs waits for them one tile before the rest of this set is needed
       const int rt = tid - 128;  // lanes 128-255: channel rt & 31, pooled row rt >> 5
       const int c = rt & 31, wy = (rt >> 5) & 3;
-      const bool row = (rt >= 0) & ((uint32_t)(py0 + wy) < (uint32_t)Q);
-      const bool lok = row & (px0 >= 0), rok = row & (px0 + 9 < Q);
-      const int64_t e0 = (int64_t)c * gplane + (int64_t)wy * Q;  // element of column 0, from rg's base
-      if constexpr (!BIG) {
-        // fp16: the 8 inner columns in one (2-B aligned) 16-B load, the halo columns in 2-B loads
-        const uint32_t o = (uint32_t)(e0 * 2);
-        rl = __builtin_amdgcn_raw_buffer_load_b16(rg, lok ? o : kBROob, 0, 0);
-        rm = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rg, row ? o + 2 : kBROob, 0, 0));
-        rr = __builtin_amdgcn_raw_buffer_load_b16(rg, rok ? o + 18 : kBROob, 0, 0);
-      } else {
-        const unsigned short* gp = a.g2m + (int64_t)b * 32 * gplane + (int64_t)py0 * Q + px0 + (row ? e0 : 0);
-        rl = lok ? gp[0] : 0u;  // (BIG: 64-bit loads; the rare >4 GiB-per-image shapes)
-        const unsigned short* mp = gp + 1;
-        rm = make_uint4((uint32_t)mp[0] | ((uint32_t)mp[1] << 16), (uint32_t)mp[2] | ((uint32_t)mp[3] << 16),
-                        (uint32_t)mp[4] | ((uint32_t)mp[5] << 16), (uint32_t)mp[6] | ((uint32_t)mp[7] << 16));
-        rr = rok ? gp[9] : 0u;
-      }
+      const bool row = (rt >= 0) & (in | ((uint32_t)(py0 + wy) < (uint32_t)Q));
+      const bool lok = row & (in | (px0 >= 0)), rok = row & (in | (px0 + 9 < Q));
+      // element of column 0, from the g2m base (!BIG: an image's planes are below 4 GiB)
+      const uint32_t e = (uint32_t)(((int64_t)c * Q * Q + (int64_t)wy * Q) * 2);
+      o.gl = lok ? e : kBROob;
+      o.gm = row ? e + 2 : kBROob;
+      o.gr = rok ? e + 18 : kBROob;
     }
     const int cb = (tid % BR_NCH) * BR_CW;  // the chunk's first channel (256 % BR_NCH == 0: every u)
 #pragma unroll
@@ -507,26 +543,11 @@ struct BRStager {
         const int lr = 2 * wy + (q >> 1), lc = 2 * wx + (q & 1);
         const int gr = R0 + lr, gc = c0 - 2 + lc;
         const bool ok = item & (in | (((uint32_t)gr < (uint32_t)P) & ((uint32_t)gc < (uint32_t)P)));
-        const uint32_t off = ok ? (uint32_t)((lr * P + lc) * 64 + cb * 2) : kBROob;
-        yv[u][q] = br_load_y(ry, off);
+        o.y[u][q] = ok ? (uint32_t)((lr * P + lc) * 64 + cb * 2) : kBROob;
       }
       const int py = py0 + wy, px = px0 + wx;
       const bool pooled = item & (in | (((uint32_t)py < (uint32_t)Q) & ((uint32_t)px < (uint32_t)Q)));
-      av[u] = __builtin_amdgcn_raw_buffer_load_b32(ra, pooled ? (uint32_t)(((wy * Q + wx) * 2 + (cb >> 4)) * 4) : kBROob, 0, 0);
-      if constexpr (GB) {
-        // (from the LDS tile in store())
-      } else if constexpr (!BIG) {
-        const uint32_t og = (uint32_t)(((int64_t)cb * gplane + (int64_t)wy * Q + wx) * 2);
-        const uint32_t gstep = (uint32_t)(gplane * 2);
-#pragma unroll
-        for (int k = 0; k < BR_CW; ++k)
-          gv[u][k] = f16_val(__builtin_amdgcn_raw_buffer_load_b16(rg, pooled ? og + k * gstep : kBROob, 0, 0));
-      } else {
-        const unsigned short* gp =
-            a.g2m + ((int64_t)b * 32 + cb) * gplane + (int64_t)(pooled ? py : 0) * Q + (pooled ? px : 0);
-#pragma unroll
-        for (int k = 0; k < BR_CW; ++k) gv[u][k] = f16_val(gp[k * gplane]);  // masked at use (store: pooled)
-      }
+      o.a[u] = pooled ? (uint32_t)(((wy * Q + wx) * 2 + (cb >> 4)) * 4) : kBROob;
     }
 #pragma unroll
     for (int j = 0; j < PPER; ++j) {
@@ -535,9 +556,87 @@ struct BRStager {
       const int lr = rec / BR_SC, lc = rec - lr * BR_SC;
       const int gr = R0 + lr, gc = c0 - 2 + lc;
       const bool ok = (e < PIECES) & (in | (((uint32_t)gr < (uint32_t)P) & ((uint32_t)gc < (uint32_t)P)));
-      const uint32_t off = ok ? (uint32_t)((lr * P + lc) * 32 + q * 16) : kBROob;
-      pr[j] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rp, off, 0, 0));
+      o.p[j] = ok ? (uint32_t)((lr * P + lc) * 32 + q * 16) : kBROob;
     }
+    return o;
+  }
+
+  __device__ __forceinline__ void load(const BRArgs& a, int b, int R0, int c0, int tid) {
+    issue(a, bases(a, b, R0, c0), offsets(a, R0, c0, tid, interior(a, R0, c0)), tid);
+  }
+
+  // the block's loads, from its bases and lane offsets: ONE path for interior and border blocks
+  __device__ __forceinline__ void issue(const BRArgs& a, const Bases& bs, const Offs& o, int tid) {
+    if constexpr (br_no_gload(DIAG)) {
+#pragma unroll
+      for (int u = 0; u < IPER; ++u) {
+#pragma unroll
+        for (int k = 0; k < BR_CW; ++k) gv[u][k] = 0.f;
+        av[u] = 0u;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) yv[u][q] = BRY{};
+      }
+#pragma unroll
+      for (int j = 0; j < PPER; ++j) pr[j] = make_uint4(0u, 0u, 0u, 0u);
+      return;
+    }
+    const int Q = a.Q;
+    // one descriptor per block and tensor; lanes outside the image -> kBROob
+    const __amdgpu_buffer_rsrc_t ry = tds_buffer_rsrc(reinterpret_cast<const void*>(bs.y), 0xFFFFFFF0u);
+    const __amdgpu_buffer_rsrc_t rp = tds_buffer_rsrc(reinterpret_cast<const void*>(bs.p), 0xFFFFFFF0u);
+    const __amdgpu_buffer_rsrc_t rg = tds_buffer_rsrc(reinterpret_cast<const void*>(bs.g), 0xFFFFFFF0u);
+    const __amdgpu_buffer_rsrc_t ra = tds_buffer_rsrc(reinterpret_cast<const void*>(bs.a), 0xFFFFFFF0u);
+    const int64_t gplane = (int64_t)Q * Q;
+    const unsigned short* gbase = reinterpret_cast<const unsigned short*>(bs.g);
+    if constexpr (GB) {
+      // the runs first: put_runs waits for them one tile before the rest of this set is needed
+      if constexpr (!BIG) {
+        // fp16: the 8 inner columns in one (2-B aligned) 16-B load, the halo columns in 2-B loads
+        rl = __builtin_amdgcn_raw_buffer_load_b16(rg, o.gl, 0, 0);
+        rm = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rg, o.gm, 0, 0));
+        rr = __builtin_amdgcn_raw_buffer_load_b16(rg, o.gr, 0, 0);
+      } else {
+        const int rt = tid - 128;
+        const int c = rt & 31, wy = (rt >> 5) & 3;
+        const bool row = o.gm != kBROob, lok = o.gl != kBROob, rok = o.gr != kBROob;
+        const int64_t e0 = (int64_t)c * gplane + (int64_t)wy * Q;  // element of column 0, from the base
+        const unsigned short* gp = gbase + (row ? e0 : 0);
+        rl = lok ? gp[0] : 0u;  // (BIG: 64-bit loads; the rare >4 GiB-per-image shapes)
+        const unsigned short* mp = gp + 1;
+        rm = make_uint4((uint32_t)mp[0] | ((uint32_t)mp[1] << 16), (uint32_t)mp[2] | ((uint32_t)mp[3] << 16),
+                        (uint32_t)mp[4] | ((uint32_t)mp[5] << 16), (uint32_t)mp[6] | ((uint32_t)mp[7] << 16));
+        rr = rok ? gp[9] : 0u;
+      }
+    }
+    const int cb = (tid % BR_NCH) * BR_CW;
+#pragma unroll
+    for (int u = 0; u < IPER; ++u) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) yv[u][q] = br_load_y(ry, o.y[u][q]);
+      av[u] = __builtin_amdgcn_raw_buffer_load_b32(ra, o.a[u], 0, 0);
+      if constexpr (GB) {
+        // (from the LDS tile in store())
+      } else {
+        int wy, wx;
+        item_geom(tid + 256 * u, wy, wx);
+        const bool pooled = o.a[u] != kBROob;
+        if constexpr (!BIG) {
+          const uint32_t og = (uint32_t)(((int64_t)cb * gplane + (int64_t)wy * Q + wx) * 2);
+          const uint32_t gstep = (uint32_t)(gplane * 2);
+#pragma unroll
+          for (int k = 0; k < BR_CW; ++k)
+            gv[u][k] = f16_val(__builtin_amdgcn_raw_buffer_load_b16(rg, pooled ? og + k * gstep : kBROob, 0, 0));
+        } else {
+          // (a border block's origin may lie outside the tensor: an unpooled item reads the tensor's
+          // first element instead, masked at use -- store: pooled)
+          const unsigned short* gp = pooled ? gbase + ((int64_t)cb * gplane + (int64_t)wy * Q + wx) : a.g2m;
+#pragma unroll
+          for (int k = 0; k < BR_CW; ++k) gv[u][k] = f16_val(gp[pooled ? k * gplane : 0]);
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < PPER; ++j) pr[j] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rp, o.p[j], 0, 0));
   }
 
   // GB: this set's runs into the LDS tile gb ([pooled row][col][channel])
@@ -741,16 +840,35 @@ __device__ __forceinline__ void br_stage(const BRArgs& a, char* smem) {
   auto tile = [&](int j) { return br_decode(a.walk, j, a.sk, a.w); };
   // (the staging waves run at priority 0: with three sets in flight the look-ahead loads no longer
   // need a raised priority, r5_s13: isolated 0.668 -> 0.659 ms without it)
-  auto ld = [&](Set& s, int j) {
-    const BRTile x = tile(j);
-    s.load(a, x.b, x.r0 + 2, x.c0, tid);
+  // The look-ahead loads' addressing is carried, not rebuilt per tile (the staging waves' instruction
+  // stream is what the consumers wait for at the per-tile barrier):
+  //  - each set keeps the walk entry it was loaded for (ent: stage_if decodes that, no second
+  //    load), and the entry of the NEXT tile to load is fetched a tile early (ahead: tile j + 1 at
+  //    ld(j); the list's BR_WALK_PAD end entries cover the last one, kk + 7);
+  //  - the four descriptor bases follow the walk down a segment by constants (run += step); a
+  //    segment start or an end entry rebuilds them, under a wave-uniform branch of SALU only;
+  //  - the lanes' offsets of an interior block are computed once (lane); only a border block selects
+  //    per lane by its bounds, again without a load under the branch.
+  const typename Set::Offs lane = Set::offsets(a, 0, 0, tid, true);
+  const typename Set::Steps step = Set::steps(a);
+  typename Set::Bases run{};
+  uint32_t ahead = br_entry(a.walk, 1, a.sk);
+  auto ld = [&](Set& s, uint32_t& ent, int j, bool first) {
+    ent = ahead;
+    ahead = br_entry(a.walk, j + 1, a.sk);
+    const BRTile x = br_tile(ent);
+    if (first | x.start | x.end) run = Set::bases(a, x.b, x.r0 + 2, x.c0);
+    else run = Set::next_down(run, step);
+    typename Set::Offs o = lane;
+    if (!Set::interior(a, x.r0 + 2, x.c0)) o = Set::offsets(a, x.r0 + 2, x.c0, tid, false);
+    s.issue(a, run, o, tid);
   };
   // stage tile j from set s if it exists (a segment start also gets its prologue: after the set is
   // stored and before it is reloaded, so its registers are the set's); false past the list's end
   // nxt (the set holding tile j+1) puts its g2m runs into tile j+1's LDS tile; they are read
   // after the next barrier, and that tile's previous contents (tile j-1) were read before this one
-  auto stage_if = [&](Set& s, Set& nxt, int j) {
-    const BRTile x = tile(j);
+  auto stage_if = [&](Set& s, Set& nxt, uint32_t ent, int j) {
+    const BRTile x = br_tile(ent);
     if (!x.end) {
       stage(s, j, x);
       nxt.put_runs(gbuf(j + 1), tid);
@@ -759,6 +877,7 @@ __device__ __forceinline__ void br_stage(const BRArgs& a, char* smem) {
     return !x.end;
   };
   Set st0, st1, st2;
+  uint32_t ent0, ent1, ent2;  // the walk entries the sets were loaded for
   {
     const BRTile x0 = tile(0);
     if (!x0.end) {  // tile 0: its own synchronous set, g2m per item (no LDS tile precedes it)
@@ -769,30 +888,31 @@ __device__ __forceinline__ void br_stage(const BRArgs& a, char* smem) {
       prologue(0, x0);
     }
   }
-  ld(st1, 1);
-  ld(st2, 2);
-  ld(st0, 3);
+  ld(st1, ent1, 1, true);
+  ld(st2, ent2, 2, false);
+  ld(st0, ent0, 3, false);
   st1.put_runs(gbuf(1), tid);  // tile 1's, read after the loop's first barrier
   // iteration kk: tile kk+1 from st1 (reload: kk+4), kk+2 from st2 (kk+5), kk+3 from st0 (kk+6);
   // one exit and every set reloaded on every path (the two-set loop's rule, below).  The walk
-  // table carries BR_WALK_PAD end entries: the last iteration (kk <= n-1) reads tile kk + 6.
+  // table carries BR_WALK_PAD end entries: the last iteration (kk <= n-1) loads tile kk + 6
+  // and fetches the entry of kk + 7.
   bool more = !tile(0).end;
   for (int kk = 0; more; kk += 3) {
     clk.barrier();  // consumers start tile kk
-    const bool has1 = stage_if(st1, st2, kk + 1);
-    ld(st1, kk + 4);
+    const bool has1 = stage_if(st1, st2, ent1, kk + 1);
+    ld(st1, ent1, kk + 4, false);
     bool has2 = false;
     if (has1) {
       clk.barrier();  // tile kk + 1
-      has2 = stage_if(st2, st0, kk + 2);
+      has2 = stage_if(st2, st0, ent2, kk + 2);
     }
-    ld(st2, kk + 5);
+    ld(st2, ent2, kk + 5, false);
     bool has3 = false;
     if (has2) {
       clk.barrier();  // tile kk + 2
-      has3 = stage_if(st0, st1, kk + 3);
+      has3 = stage_if(st0, st1, ent0, kk + 3);
     }
-    ld(st0, kk + 6);
+    ld(st0, ent0, kk + 6, false);
     more = has3;
   }
   clk.barrier();
@@ -814,6 +934,7 @@ __global__ __launch_bounds__(BR_THREADS, 2) void conv2_bwd_roll_kernel(
   a.y2 = y2; a.a2 = a2; a.g2m = g2m; a.p1 = p1; a.dp1 = dp1; a.slab = slab; a.walk = walk;
   a.B = B; a.P = P; a.Q = P / 2;
   a.sk = sk;
+  a.rows = sw;
   a.w = xcd_remap(blockIdx.x, gridDim.x);  // this workgroup's list (XCD-contiguous: neighbouring columns)
   a.walk = walk + a.w * sw;
   float* kc = reinterpret_cast<float*>(smem + BR_OFF_K);
