@@ -436,6 +436,118 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> fused_conv2_forward_bn(
   return {y2, ya, a2, stats, aff};
 }
 
+// ---------------------------------------------------------------- inference plan
+// (models/convnet_fused.py forward_inference: constants -> layer 1 -> conv2 -> fused_head_forward_aff)
+// The BN affines from the running statistics and p1's range guard (kernels/inference.hip): returns
+// (aff1 [33]: a16 | b16 | p1 scale, aff2 [64]: a32 | b32) and stores 1 / p1 scale at mag[kMagScales + 1]
+// (conv2_pack(write_p1=False) on the same mag goes first: it zeroes the bounds and writes the other
+// scales).  An fp32 x is read once for max |x|; uint8 levels are bounded without a read.  No BN
+// buffer is written.
+std::tuple<Tensor, Tensor> inference_constants(const Tensor& x, const Tensor& w1, const Tensor& b1, const Tensor& g1,
+                                               const Tensor& be1, const Tensor& rm1, const Tensor& rv1, double eps1,
+                                               const Tensor& g2, const Tensor& be2, const Tensor& rm2,
+                                               const Tensor& rv2, double eps2, const Tensor& mag) {
+  check_l1_input(x, "inference_constants");
+  need(w1, at::kFloat, {16, 1, 5, 5}, "conv1.weight");
+  need(b1, at::kFloat, {16}, "conv1.bias");
+  need(g1, at::kFloat, {16}, "bn1.weight");
+  need(be1, at::kFloat, {16}, "bn1.bias");
+  need(rm1, at::kFloat, {16}, "bn1.running_mean");
+  need(rv1, at::kFloat, {16}, "bn1.running_var");
+  need(g2, at::kFloat, {32}, "bn2.weight");
+  need(be2, at::kFloat, {32}, "bn2.bias");
+  need(rm2, at::kFloat, {32}, "bn2.running_mean");
+  need(rv2, at::kFloat, {32}, "bn2.running_var");
+  uint32_t* m = opt_mag(mag, kMagScales + 4);
+  TORCH_CHECK(m != nullptr, "inference_constants: mag is required");
+  c10::DeviceGuard guard(x.device());
+  hipStream_t st = stream_of(x);
+  auto fo = x.options().dtype(at::kFloat);
+  auto aff1 = at::empty({33}, fo);
+  auto aff2 = at::empty({64}, fo);
+  Tensor xpart;
+  int nxp = 0;
+  if (x.scalar_type() == at::kFloat) {
+    TORCH_CHECK(x.numel() % 4 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+                "inference_constants: an fp32 x must be 16-B aligned with W % 4 == 0");
+    const int64_t n4 = x.numel() / 4;
+    nxp = tds_x_absmax_num_wg(n4);
+    xpart = at::empty({nxp}, fo.dtype(at::kInt));
+    tds_x_absmax(x.data_ptr<float>(), n4, reinterpret_cast<uint32_t*>(xpart.data_ptr<int>()), nxp, st);
+  }
+  tds_inference_constants(nxp ? reinterpret_cast<const uint32_t*>(xpart.data_ptr<int>()) : nullptr, nxp,
+                          w1.data_ptr<float>(), b1.data_ptr<float>(), g1.data_ptr<float>(), be1.data_ptr<float>(),
+                          rm1.data_ptr<float>(), rv1.data_ptr<float>(), (float)eps1, g2.data_ptr<float>(),
+                          be2.data_ptr<float>(), rm2.data_ptr<float>(), rv2.data_ptr<float>(), (float)eps2,
+                          aff1.data_ptr<float>(), aff2.data_ptr<float>(), m, st);
+  check_launches("inference_constants");
+  return {aff1, aff2};
+}
+
+// The layer-1 launch on a given affine (inference_constants' aff1): p1 [B,P,P,16] fp16 only -- the
+// argmax / ReLU-mask plane idx1 is neither allocated nor stored.
+Tensor fused_l1_forward_inference(const Tensor& x, const Tensor& w1, const Tensor& b1, const Tensor& aff1) {
+  check_l1_input(x, "fused_l1_forward_inference");
+  TORCH_CHECK(x.size(2) % 4 == 0, "fused_l1_forward_inference: H % 4 == 0 required");
+  need(w1, at::kFloat, {16, 1, 5, 5}, "conv1.weight");
+  need(b1, at::kFloat, {16}, "conv1.bias");
+  need(aff1, at::kFloat, {33}, "aff1");
+  TORCH_CHECK(x.scalar_type() == at::kByte || reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "fused_l1_forward_inference: an fp32 x must be 16-B aligned");
+  const int64_t B = x.size(0), H = x.size(2), W = x.size(3);
+  c10::DeviceGuard guard(x.device());
+  auto p1 = at::empty({B, H / 2, W / 2, 16}, x.options().dtype(at::kHalf));
+  tds_l1_apply_inference(x.data_ptr(), x.scalar_type() == at::kByte, w1.data_ptr<float>(), b1.data_ptr<float>(),
+                         aff1.data_ptr<float>(), p1.data_ptr(), l1_wg(), (int)B, (int)H, (int)W, stream_of(x));
+  check_launches("fused_l1_forward_inference");
+  return p1;
+}
+
+// The conv2 forward's inference variant (conv2_fwd2.hip): ya [B,32,PB] fp16 only, bit-identical to
+// fused_conv2_forward_bn's on the same p1 / wp / gamma2 / mag scales; y2h and a2 are not allocated.
+Tensor fused_conv2_forward_inference(const Tensor& p1, const Tensor& wp, const c10::optional<Tensor>& gamma2,
+                                     const c10::optional<Tensor>& mag) {
+  TORCH_CHECK(p1.dim() == 4 && p1.size(1) == p1.size(2) && p1.size(3) == 16,
+              "fused_conv2_forward_inference: p1 [B,P,P,16]");
+  const int64_t B = p1.size(0), P = p1.size(1);
+  need(p1, at::kHalf, {B, P, P, 16}, "p1");
+  need(wp, at::kShort, {13 * 2 * 4 * 16 * 8}, "conv2 fwd pack");
+  const float* g = optf(gamma2, 32, "bn2.weight");
+  TORCH_CHECK(B >= 1 && B <= 255 && P >= 2, "fused_conv2_forward_inference: 1 <= batch <= 255 and P >= 2");
+  c10::DeviceGuard guard(p1.device());
+  const int nwg = tds_conv2_fwd2_num_wg();
+  int tr = 0, tc = 0;
+  tds_conv2_fwd2_tiles((int)P, &tr, &tc);
+  int sw = 0, sk = 0;
+  const int* order = tile_order(p1, (int)B, tr, tc, nwg, &sw, &sk);
+  auto ya = at::empty({B, 32, pb_plane(P)}, p1.options().dtype(at::kHalf));
+  uint32_t* m = opt_mag(mag, kMagScales + 3);
+  tds_conv2_fwd2_inference(p1.data_ptr(), wp.data_ptr<int16_t>(), g, ya_out(ya), m ? m + kMagScales : nullptr, order,
+                           nwg, sw, sk, (int)B, (int)P, stream_of(p1));
+  check_launches("fused_conv2_forward_inference");
+  return ya;
+}
+
+// Evaluation metrics of one batch added to a device accumulator acc (int64 [3], zeroed by the
+// caller): acc[0] holds the BITS of the fp64 sum of per-sample cross-entropy losses, acc[1] the
+// samples whose argmax (lowest index on a tie; a row with a NaN is wrong) equals the label, acc[2]
+// the samples counted.  No host synchronisation: the caller reads acc once at the end.
+void eval_metrics(const Tensor& logits, const Tensor& labels, const Tensor& acc) {
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) >= 1 && logits.size(1) >= 1 && logits.size(0) <= INT32_MAX &&
+                  logits.size(1) <= INT32_MAX,
+              "eval_metrics: logits must be [M >= 1, N >= 1]");
+  const int64_t M = logits.size(0), N = logits.size(1);
+  need(logits, at::kFloat, {M, N}, "logits");
+  need(labels, at::kLong, {M}, "labels");
+  need(acc, at::kLong, {3}, "acc");
+  TORCH_CHECK(labels.device() == logits.device() && acc.device() == logits.device(),
+              "eval_metrics: logits, labels and acc must be on one device");
+  c10::DeviceGuard guard(logits.device());
+  tds_eval_metrics(logits.data_ptr<float>(), labels.data_ptr<int64_t>(), (int)M, (int)N, -100,
+                   reinterpret_cast<unsigned long long*>(acc.data_ptr<int64_t>()), stream_of(logits));
+  check_launches("eval_metrics");
+}
+
 // The head forward on a finished BN2 affine (fused_conv2_forward_bn's aff2): logits only, finished
 // inside the head's launch (head_pb.hip HPFin) for B <= 8
 Tensor fused_head_forward_aff(const Tensor& ya, const Tensor& aff2, const Tensor& b2, const c10::optional<Tensor>& mag,
@@ -1187,6 +1299,15 @@ TORCH_LIBRARY_FRAGMENT(tdsa, m) {
       "Tensor(b!)? rv2, Tensor(c!)? nbt2, float momentum, float eps, Tensor(d!)? mag=None) -> "
       "(Tensor, Tensor, Tensor, Tensor, Tensor)",
       &fused_conv2_forward_bn);
+  m.def(
+      "inference_constants(Tensor x, Tensor w1, Tensor b1, Tensor g1, Tensor be1, Tensor rm1, Tensor rv1, float eps1, "
+      "Tensor g2, Tensor be2, Tensor rm2, Tensor rv2, float eps2, Tensor(a!) mag) -> (Tensor, Tensor)",
+      &inference_constants);
+  m.def("fused_l1_forward_inference(Tensor x, Tensor w1, Tensor b1, Tensor aff1) -> Tensor",
+        &fused_l1_forward_inference);
+  m.def("fused_conv2_forward_inference(Tensor p1, Tensor wp, Tensor? gamma2, Tensor? mag=None) -> Tensor",
+        &fused_conv2_forward_inference);
+  m.def("eval_metrics(Tensor logits, Tensor labels, Tensor(a!) acc) -> ()", &eval_metrics);
   m.def("fused_head_forward_aff(Tensor ya, Tensor aff2, Tensor b2, Tensor? mag, Tensor wfc, Tensor? bfc, int P, "
         "Tensor(a!)? x_out=None) -> Tensor",
         &fused_head_forward_aff);

@@ -9,6 +9,28 @@
 
 namespace tds {
 
+// One row's loss by one wave (every lane calls it, every lane gets it): the arithmetic of
+// ce_small_block's row loop below, step for step, without the dlogits -- the evaluation metrics
+// (inference.hip eval_metrics_kernel) sum it per sample.  valid: the label is not ignore_index.
+// (ce_small_block keeps its own copy of these lines: routed through this helper the head forward's
+// and ce_small_kernel's code came out with another register allocation, and the training kernels
+// are to stay as they were.)
+__device__ __forceinline__ float ce_row_loss(const float* z, int N, int64_t lab, int64_t ignore_index, float eps,
+                                             int lane, bool& valid) {
+  float mx = -INFINITY;
+  for (int j = lane; j < N; j += TDS_WAVE) mx = fmaxf(mx, z[j]);
+  mx = wave_max(mx);
+  float sm = 0.f, zsum = 0.f;
+  for (int j = lane; j < N; j += TDS_WAVE) { sm += __expf(z[j] - mx); zsum += z[j]; }
+  sm = wave_sum(sm);
+  zsum = wave_sum(zsum);
+  const float lse = mx + __logf(sm);
+  valid = lab != ignore_index;
+  const bool bad = valid && (lab < 0 || lab >= N);
+  const int64_t lz = bad ? 0 : lab;
+  return bad ? NAN : valid ? (1.f - eps) * (lse - z[lz]) + eps * (lse - zsum / (float)N) : 0.f;
+}
+
 __device__ __forceinline__ void ce_small_block(const float* logits, const int64_t* __restrict__ labels,
                                                float* __restrict__ dlogits, float* __restrict__ loss_out,
                                                float* __restrict__ inv_count_out, int M, int N,

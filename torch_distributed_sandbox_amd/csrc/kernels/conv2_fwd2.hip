@@ -499,6 +499,108 @@ __global__ __launch_bounds__(F2_THREADS, F2_WG) void conv2_fwd2_kernel(const uin
   }
 }
 
+// ---------------------------------------------------------------------------- inference variant
+// The forward of the inference plan (models/convnet_fused.py forward_inference): BN2 runs on its
+// running statistics and nothing is saved for a backward, so only ya leaves the kernel -- no y2h
+// staging or stores (64 B per conv2 pixel), no a2 codes, no BN2 partials, no ypart maxima and no
+// finalizer.  Tiling, LDS-DMA staging and the MFMA schedule are the training kernel's (f2_dma,
+// f2_compute); the epilogue is the pooled-block part of f2_stage, value for value, so ya comes out
+// bit-identical to conv2_fwd2_kernel's on the same p1, packed weights and gamma2.  A kernel symbol of
+// its own: the training instantiations are compiled exactly as before.
+constexpr int F2I_YSTAGE = 32 * 32 * 4;             // pooled block: 32 co x 4 x 8 words
+constexpr int F2I_OFF_Y = 2 * F2_PBUF;              // p1 double buffer first
+constexpr int F2I_LDS = F2I_OFF_Y + 2 * F2I_YSTAGE;  // 24 KiB
+static_assert(F2I_LDS % 16 == 0 && F2_WG * F2I_LDS <= 160 * 1024, "LDS carve");
+
+// the tile's pooled windows -> the staged ya block (f2_stage's window part: the same extreme, the
+// same rounding)
+template <bool PLAIN>
+__device__ __forceinline__ void f2i_pool(const f32x4 (&acc)[4], float* ystage, int RH, int NT, int lane, float ksc,
+                                         bool neg, bool zg) {
+  const int li = lane & 15, g = lane >> 4;
+  const int co = 16 * NT + li;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    uint32_t e[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const float v0 = acc[2 * i][2 * j], v1 = acc[2 * i][2 * j + 1], v2 = acc[2 * i + 1][2 * j];
+      const float v3 = acc[2 * i + 1][2 * j + 1];
+      float m;
+      if constexpr (PLAIN)
+        m = __builtin_elementwise_maximum(__builtin_elementwise_maximum(v0, v1), __builtin_elementwise_maximum(v2, v3));
+      else
+        m = zg ? v0 : f2_ext4(v0, v1, v2, v3, neg);  // gamma2 == 0: the first position (torch's max-pool)
+      e[j] = f16_bits(m * ksc);
+    }
+    *reinterpret_cast<uint2*>(ystage + f2_ystage_off(co, (2 * RH + i) * 8 + 2 * g)) = make_uint2(e[0], e[1]);
+  }
+}
+
+template <int WV>
+__device__ __forceinline__ void f2i_run(const uint4* __restrict__ p1, const uint4* __restrict__ wpack,
+                                        const float* __restrict__ gamma, unsigned short* __restrict__ ya,
+                                        const uint32_t* __restrict__ scales, const int* __restrict__ order, int sw,
+                                        int sk, int B, int P, char* smem) {
+  constexpr int NT = WV & 1, RH = WV >> 1;
+  const int lane = threadIdx.x & 63, li = lane & 15;
+  const int tiles_c = (P + F2_TC - 1) / F2_TC, tiles_r = (P + F2_TH - 1) / F2_TH;
+  const int total = tiles_c * tiles_r * B;
+  const int w = xcd_remap(blockIdx.x, gridDim.x);
+  const int* __restrict__ mine = order + w * sw;
+  auto decode = [&](int kk) {
+    F2Tile x;
+    int tr, tc;
+    tile_from_order(mine, kk * sk, x.b, tr, tc);
+    x.r0 = tr * F2_TH;
+    x.c0 = tc * F2_TC;
+    return x;
+  };
+  f32x4 W[13];
+#pragma unroll
+  for (int s = 0; s < 13; ++s) W[s] = __builtin_bit_cast(f32x4, wpack[(s * 2 + NT) * 64 + lane]);
+  const float ksc = scales != nullptr ? __uint_as_float(scales[2]) : 1.f;  // ya's store factor (y2h's)
+  const bool neg = gamma != nullptr && gamma[16 * NT + li] < 0.f;
+  const bool zg = gamma != nullptr && gamma[16 * NT + li] == 0.f;
+  const bool plain = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_ballot_w64(neg || zg) == 0 ? 1 : 0) != 0;
+  const PBGeom pg = pb_geom(P / 2);
+  float* ys = reinterpret_cast<float*>(smem + F2I_OFF_Y);
+  f32x4 acc[4];
+  F2Tile prev{0, 0, 0};
+  bool have_prev = false;
+  int t = w;
+  if (t < total) f2_dma<0, WV>(p1, decode(0), P, smem, lane);
+  int kk = 0;
+  for (; t < total; t += gridDim.x, ++kk) {
+    const F2Tile cur = decode(kk);
+    // tile t's DMA landed; p1 buffer (kk+1)&1 is free; the pooled block of tile t-1 is staged
+    __syncthreads();
+    if (t + (int)gridDim.x < total) f2_dma<0, WV>(p1, decode(kk + 1), P, smem + ((kk + 1) & 1) * F2_PBUF, lane);
+    if (have_prev) f2_store_ya(ys + ((kk + 1) & 1) * (F2I_YSTAGE / 4), prev, ya, pg);
+    f2_compute<0>(smem + (kk & 1) * F2_PBUF, W, acc, RH, lane);
+    if (plain)  // wave-uniform
+      f2i_pool<true>(acc, ys + (kk & 1) * (F2I_YSTAGE / 4), RH, NT, lane, ksc, neg, zg);
+    else
+      f2i_pool<false>(acc, ys + (kk & 1) * (F2I_YSTAGE / 4), RH, NT, lane, ksc, neg, zg);
+    prev = cur;
+    have_prev = true;
+  }
+  __syncthreads();
+  if (have_prev) f2_store_ya(ys + ((kk - 1) & 1) * (F2I_YSTAGE / 4), prev, ya, pg);
+}
+
+__global__ __launch_bounds__(F2_THREADS, F2_WG) void conv2_fwd2_inference_kernel(
+    const uint4* __restrict__ p1, const uint4* __restrict__ wpack, const float* __restrict__ gamma,
+    unsigned short* __restrict__ ya, const uint32_t* __restrict__ scales, const int* __restrict__ order, int sw, int sk,
+    int B, int P) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform role
+  if (wv == 0) f2i_run<0>(p1, wpack, gamma, ya, scales, order, sw, sk, B, P, smem);
+  else if (wv == 1) f2i_run<1>(p1, wpack, gamma, ya, scales, order, sw, sk, B, P, smem);
+  else if (wv == 2) f2i_run<2>(p1, wpack, gamma, ya, scales, order, sw, sk, B, P, smem);
+  else f2i_run<3>(p1, wpack, gamma, ya, scales, order, sw, sk, B, P, smem);
+}
+
 }  // namespace tds
 
 using namespace tds;
@@ -526,6 +628,16 @@ static int f2_diag_env() { return 0; }
 // (fused_ops.cpp tile_order, sw / sk: the strides of workgroup / tile), allocated by the caller
 int tds_conv2_fwd2_fin_doubles(int nwg) { return ((nwg + F2_GROUP - 1) / F2_GROUP) * 32 * 2; }
 int tds_conv2_fwd2_fin_words(int nwg) { return ((nwg + F2_GROUP - 1) / F2_GROUP) * 32; }
+
+// the inference variant: ya only (order / nwg / sw / sk as tds_conv2_fwd2)
+void tds_conv2_fwd2_inference(const void* p1, const short* wp, const float* gamma, unsigned short* ya,
+                              const uint32_t* scales, const int* order, int nwg, int sw, int sk, int B, int P,
+                              hipStream_t st) {
+  hipLaunchKernelGGL(conv2_fwd2_inference_kernel, dim3(nwg), dim3(F2_THREADS), F2I_LDS, st,
+                     reinterpret_cast<const uint4*>(p1), reinterpret_cast<const uint4*>(wp), gamma, ya, scales, order, sw,
+                     sk, B, P);
+  TDS_LAUNCH_CHECK();
+}
 
 void tds_conv2_fwd2(const void* p1, const short* wp, const float* bias, const float* gamma, void* y2h, unsigned short* ya,
                     uint32_t* a2, double* partial, uint32_t* ypart, const uint32_t* scales, const int* order, int nwg, int sw, int sk,

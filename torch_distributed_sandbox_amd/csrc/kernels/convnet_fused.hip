@@ -85,7 +85,8 @@ __device__ __forceinline__ L1Pair l1_pair(int g, int p) {
 // LV: x holds uint8 levels (x = L1_LEVEL_SCALE * level).  A level is exact in bf16, so the LDS word
 // is the level's fp32 bit pattern (bf16 hi | lo = 0), conv1 takes two MFMAs (w hi, w lo) per
 // product instead of three and half the operand perms, and the scale folds into BN1's affine.
-template <bool LV>
+// IDX = false (the inference plan, nothing saved for a backward): p1 only, idx1 is never touched.
+template <bool LV, bool IDX = true>
 __global__ __launch_bounds__(256) void l1_conv_bf3_kernel(const void* __restrict__ xv, const float* __restrict__ w1,
                                                       const float* __restrict__ b1, const float* __restrict__ aff,
                                                       uint4* __restrict__ p1, uint8_t* __restrict__ idx1, int B,
@@ -317,7 +318,7 @@ __global__ __launch_bounds__(256) void l1_conv_bf3_kernel(const void* __restrict
           // (non-temporal: plain, allocating p1 stores cost the layer-1 conv +14 us and the conv2
           // forward +23 us, r5_s44)
           st_stream(dst + g, make_uint2(h01, h23));
-          st_stream(reinterpret_cast<uint32_t*>(idx1 + rec * 16) + g, ixw);
+          if constexpr (IDX) st_stream(reinterpret_cast<uint32_t*>(idx1 + rec * 16) + g, ixw);
         }
       }
     }
@@ -1274,6 +1275,19 @@ void tds_l1_apply(const void* x, bool levels, const float* w1, const float* b1, 
   else
     hipLaunchKernelGGL(l1_conv_bf3_kernel<false>, dim3(nwg), dim3(256), 0, st, x, w1, b1, aff,
                        reinterpret_cast<uint4*>(p1), idx1, B, H, W);
+  TDS_LAUNCH_CHECK();
+}
+
+// the inference plan's layer-1 launch: the same kernel on the running-statistics affine
+// (inference.hip), p1 only
+void tds_l1_apply_inference(const void* x, bool levels, const float* w1, const float* b1, const float* aff, void* p1,
+                            int nwg, int B, int H, int W, hipStream_t st) {
+  if (levels)
+    hipLaunchKernelGGL((l1_conv_bf3_kernel<true, false>), dim3(nwg), dim3(256), 0, st, x, w1, b1, aff,
+                       reinterpret_cast<uint4*>(p1), static_cast<uint8_t*>(nullptr), B, H, W);
+  else
+    hipLaunchKernelGGL((l1_conv_bf3_kernel<false, false>), dim3(nwg), dim3(256), 0, st, x, w1, b1, aff,
+                       reinterpret_cast<uint4*>(p1), static_cast<uint8_t*>(nullptr), B, H, W);
   TDS_LAUNCH_CHECK();
 }
 

@@ -106,6 +106,11 @@ int tds_conv2_fwd2_fin_words(int nwg);
 void tds_conv2_fwd2(const void* p1, const short* wp, const float* bias, const float* gamma, void* y2h, unsigned short* ya,
                     uint32_t* a2, double* partial, uint32_t* ypart, const uint32_t* scales, const int* order, int nwg, int sw, int sk,
                     int B, int P, hipStream_t st, const TdsBnFin* bn = nullptr);
+// the inference variant (running-statistics BN2, nothing saved for a backward): ya only, bit-identical
+// to tds_conv2_fwd2's on the same p1 / wp / gamma / scales; order, nwg, sw, sk as there
+void tds_conv2_fwd2_inference(const void* p1, const short* wp, const float* gamma, unsigned short* ya,
+                              const uint32_t* scales, const int* order, int nwg, int sw, int sk, int B, int P,
+                              hipStream_t st);
 int tds_conv2_bwd3_num_wg();  // slab rows the backward writes (workgroups it launches)
 void tds_conv2_bwd3_tiles(int P, int* tiles_r, int* tiles_c);
 // rolling-window backward (conv2_bwd.hip): walk = tds_conv2_bwd_walk table for nwg workgroups
@@ -130,6 +135,9 @@ void tds_l1_gram(const double* ac_sum, const double* strips, const void* x, bool
 // levels: x is uint8 levels (x = level / 255, convnet_fused.hip L1_LEVEL_SCALE), else fp32
 void tds_l1_apply(const void* x, bool levels, const float* w1, const float* b1, const float* aff, void* p1,
                   uint8_t* idx1, int nwg, int B, int H, int W, hipStream_t st);
+// l1_conv_bf3_kernel without the argmax / ReLU-mask plane (the inference plan): p1 only
+void tds_l1_apply_inference(const void* x, bool levels, const float* w1, const float* b1, const float* aff, void* p1,
+                            int nwg, int B, int H, int W, hipStream_t st);
 void tds_bn_finalize_shifted(const double* partial, int C, int nchunk, int64_t n, const float* shift, float eps,
                              float momentum, const float* gamma, const float* beta, float* stats, float* running_mean,
                              float* running_var, int64_t* num_batches, float* aff, hipStream_t st);
@@ -182,6 +190,20 @@ bool tds_l1_reduce_gram(const double* ac_part, int nchunk, double* ac_sum, doubl
 void tds_l1_finalize(const double* bwd_sum, const double* gram, int64_t n, const float* w1, const float* b1,
                      const float* gamma1, const float* stats1, float* dw1, float* db1, float* dgamma1, float* dbeta1,
                      float scale, hipStream_t st);
+
+// ---- inference.hip (the inference plan's small launches)
+int tds_x_absmax_num_wg(int64_t n4);  // partial words tds_x_absmax writes for n4 float4
+void tds_x_absmax(const float* x, int64_t n4, uint32_t* part, int nwg, hipStream_t st);  // max |x| bits per workgroup
+// aff1 [33] (a16 | b16 | p1 scale) and aff2 [64] (a32 | b32) from the running statistics, and
+// mag[kMagScales + 1] = 1 / p1 scale.  xpart (nxp words of tds_x_absmax) bounds an fp32 input;
+// nullptr: uint8 levels, |x| <= 255 / 255.  No BN buffer is written.
+void tds_inference_constants(const uint32_t* xpart, int nxp, const float* w1, const float* b1, const float* g1,
+                             const float* be1, const float* rm1, const float* rv1, float eps1, const float* g2,
+                             const float* be2, const float* rm2, const float* rv2, float eps2, float* aff1, float* aff2,
+                             uint32_t* mag, hipStream_t st);
+// acc [3] += (fp64 sum of per-sample cross-entropy | correct argmax count | samples counted)
+void tds_eval_metrics(const float* logits, const int64_t* labels, int M, int N, int64_t ignore_index,
+                      unsigned long long* acc, hipStream_t st);
 
 // ---- head_pb.hip (fc head on the pooled-blocked ya / g2m, pooled_layout.h)
 int64_t tds_pb_plane(int Q);  // floats per (image, channel) plane

@@ -45,13 +45,21 @@ def _class_templates(num_classes: int, size: int, seed: int) -> np.ndarray:
 
 
 class SyntheticMNIST:
-    """Indexable dataset of (uint8[28,28], label) pairs, fully deterministic."""
+    """Indexable dataset of (uint8[28,28], label) pairs, fully deterministic.
+
+    ``split="test"`` is held-out data of the same task: the class templates are those of ``seed``
+    (what a model trained on the train split learned), while the labels, shifts and noise come from
+    a sample stream of their own, so no test image is a training image."""
 
     def __init__(self, size: int = MNIST_TRAIN_SIZE, num_classes: int = 10, image_size: int = 28, seed: int = 0,
-                 noise: float = 0.15):
+                 noise: float = 0.15, split: str = "train"):
+        if split not in ("train", "test"):
+            raise ValueError(f"split must be train|test, got {split!r}")
         self.size, self.num_classes, self.image_size = size, num_classes, image_size
-        self.seed = seed
-        rng = np.random.default_rng(seed + 1)
+        self.seed, self.split = seed, split
+        # the sample stream: labels, then per chunk shifts and noise (the train split's is the one
+        # this class always drew from)
+        rng = np.random.default_rng(seed + 1 if split == "train" else (seed + 1, 0x7E57))
         self.labels = rng.integers(0, num_classes, size=size, dtype=np.int64)
         templ = _class_templates(num_classes, image_size, seed)
         # materialise all images once (60000*784 B = 47 MB)

@@ -13,8 +13,11 @@ Differences from the reference, by design:
   ``fc.bias``), so reference state_dicts load as-is.
 * ``forward`` picks an execution plan: on GPU in training mode the fused
   gfx950 plan (``models/convnet_fused.py``) runs the whole network as five
-  fused kernels per direction; otherwise the layer-by-layer native ops run
-  (``mode='layers'``), and on CPU the PyTorch reference ops.
+  fused kernels per direction, and in eval mode under ``no_grad`` its
+  inference plan (``convnet_fused.forward_inference``: running-statistics BN,
+  nothing saved for a backward); otherwise the layer-by-layer native ops run
+  (``mode='layers'``, eval mode with gradients enabled, a training-mode
+  ``no_grad`` forward), and on CPU the PyTorch reference ops.
 * ``forward`` also takes a uint8 batch: the resized images' levels before the
   reference's ``ToTensor`` (mnist_onegpu.py:50-52), read as ``levels / 255``
   (``to_image``).  The fused plan folds that scale into conv1 and its batch
@@ -82,19 +85,25 @@ class ConvNet(nn.Module):
         x = x.reshape(x.size(0), -1)
         return self.fc(x)
 
-    def _use_fused(self, x) -> bool:
+    def _fused_plan(self, x):
+        """The fused plan's entry point for this input (training or inference), or None."""
         if self.mode == "layers" or not x.is_cuda:
-            return False
+            return None
         from . import convnet_fused
 
-        ok = convnet_fused.supported(self, x)
-        if self.mode == "fused" and not ok:
+        if convnet_fused.supported(self, x):
+            return convnet_fused.forward
+        if convnet_fused.supported_inference(self, x):
+            return convnet_fused.forward_inference
+        if self.mode == "fused":
             raise RuntimeError("ConvNet(mode='fused'): input/config not supported by the fused plan")
-        return ok
+        return None
+
+    def _use_fused(self, x) -> bool:
+        return self._fused_plan(x) is not None
 
     def forward(self, x):
-        if self._use_fused(x):
-            from . import convnet_fused
-
-            return convnet_fused.forward(self, x)
+        plan = self._fused_plan(x)
+        if plan is not None:
+            return plan(self, x)
         return self._forward_layers(to_image(x))

@@ -1,4 +1,5 @@
-"""Fused gfx950 execution plan for the ConvNet (training mode).
+"""Fused gfx950 execution plans for the ConvNet: the training plan (``forward``) and the inference
+plan (``forward_inference``, eval mode under ``no_grad``; at the end of this module).
 
 The reference runs 13 ATen kernels forward and ~20 backward per step on
 fp32 NCHW tensors.  This plan runs the network as three
@@ -31,6 +32,12 @@ conv2 output gradient by the step's magnitude bounds ``mag``); docs/KERNELS.md "
 class".
 ``mode='layers'`` is the exact-fp32 generic path.
 
+Inference plan: the same kernels' cheap half.  BN1 / BN2 use the running statistics (one small
+launch forms both affines and p1's fp16 range guard -- a closed-form bound, Samuelson's does not hold
+for running statistics), layer 1 writes p1 only (no argmax plane), the conv2 forward's inference
+variant writes ya only (no y2h, no argmax codes, no statistics) and the training head forward runs
+unchanged on ya.  Same numerics class as above (conv2 in the TF32 class); no BN buffer is written.
+
 Gradient hand-off beside autograd: the fp16 p1 is an autograd output, but its gradient dp1 is
 fp32; the conv2 backward hands dp1 to the layer-1 backward through a link object and gives
 autograd a zero-stride fp16 placeholder (no kernel, no memory), as it does for y2.
@@ -49,6 +56,18 @@ from ..parallel import factored
 def supported(model, x) -> bool:
     if not (x.is_cuda and model.training and torch.is_grad_enabled()):
         return False
+    return _supported_config(model, x)
+
+
+def supported_inference(model, x) -> bool:
+    """The inference plan (``forward_inference``) takes what the training plan takes, in eval mode
+    under ``no_grad``."""
+    if not (x.is_cuda and not model.training and not torch.is_grad_enabled()):
+        return False
+    return _supported_config(model, x)
+
+
+def _supported_config(model, x) -> bool:
     # uint8: ToTensor's levels, x = levels / 255 folded into conv1 (models/convnet.py to_image)
     if x.dim() != 4 or x.shape[1] != 1 or x.dtype not in (torch.float32, torch.uint8):
         return False
@@ -501,3 +520,43 @@ def forward(model, x):
         link.ce = None
     link.labels = None
     return logits
+
+
+# ---- inference plan -------------------------------------------------------------------
+# Eval mode under no_grad: BN runs on its running statistics, so no moments, Gram, BN2 partials or
+# in-launch finalizer; nothing is saved for a backward, so no idx1, y2h or a2.  Five launches (six
+# for an fp32 image: one read of x for its max |x|):
+#   conv2_pack                     conv2's weights as fp16 fragments + their scales in a private mag
+#   inference_constants            BN1 / BN2 affines from the running statistics, p1's range guard
+#   fused_l1_forward_inference     l1_conv_bf3_kernel on that affine, p1 only
+#   fused_conv2_forward_inference  conv2_fwd2's inference variant, ya only
+#   fused_head_forward_aff         the training head forward, unchanged (ya's format is the same)
+# No autograd Function, link, gradient sink or exchange is involved, and every workspace (mag
+# included) is this call's own: an eval forward between a training forward and its backward leaves
+# that step as it was.
+_INFERENCE_MAG = 48  # the bounds conv2_pack zeroes (33 words) and the scales at kMagScales = 40 .. 43
+
+
+def forward_inference(model, x):
+    ops = _ext.ops()
+    conv1, bn1 = model.layer1[0], model.layer1[1]
+    conv2, bn2 = model.layer2[0], model.layer2[1]
+    fc = model.fc
+    x = x.contiguous()
+    param_fence.wait(conv2.weight)  # a deferred update of the weights (overlap_optimizer) lands first
+    mag = torch.empty(_INFERENCE_MAG, device=x.device, dtype=torch.int32)
+    wp, _ = ops.conv2_pack(conv2.weight.detach().contiguous(), mag, None, False)
+    aff1, aff2 = ops.inference_constants(x, conv1.weight, conv1.bias, bn1.weight, bn1.bias, bn1.running_mean,
+                                         bn1.running_var, float(bn1.eps), bn2.weight, bn2.bias, bn2.running_mean,
+                                         bn2.running_var, float(bn2.eps), mag)
+    p1 = ops.fused_l1_forward_inference(x, conv1.weight, conv1.bias, aff1)
+    ya = ops.fused_conv2_forward_inference(p1, wp, bn2.weight, mag)
+    # the fc update may still be running on DDP's side stream, or deferred to the next head forward
+    # (forward() above): it lands before the weight is read
+    upd = param_fence.take(fc.weight, "groups")
+    param_fence.wait(fc.weight)
+    param_fence.wait(fc.bias)
+    if upd is not None:
+        upd()  # the whole deferred update, before the weight is read
+    return ops.fused_head_forward_aff(ya, aff2, conv2.bias, mag, fc.weight, fc.bias, p1.shape[1], None)
+

@@ -7,12 +7,15 @@ model construction, ConvNet topology, bs=5, SGD(lr=1e-4), CE loss,
 local GPU 0, rank-local loss) and ``Training complete in: ...``.  Added:
 images/sec, peak memory, ``--max-steps``, synthetic on-device data, optional
 global-average loss (the reference's commented-out ``all_reduce(AVG)``,
-mnist_distributed.py:102), checkpoint/resume, fault injection.
+mnist_distributed.py:102), checkpoint/resume, fault injection, and a held-out
+evaluation after the last epoch (``--eval-size``, :func:`evaluate`; the
+reference never evaluates its model).
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import time
 from datetime import datetime
@@ -60,6 +63,11 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--bucket-mb", default=None, type=float, help="DDP bucket cap (MB, default 25 like torch)")
     p.add_argument("--reserve-cus", default=None, type=int,
                    help="rccl-native: CUs split off for the collectives (multiple of 32; default 32 at world > 1)")
+    p.add_argument("--eval-size", default=0, type=int, metavar="N",
+                   help="evaluate on N held-out samples (SyntheticMNIST split='test') after the last epoch "
+                        "(0 = no evaluation)")
+    p.add_argument("--eval-batch-size", default=None, type=int,
+                   help="per-GPU batch size of the evaluation (default: --batch-size)")
     return p
 
 
@@ -82,6 +90,83 @@ def _device(args, gpu: int) -> torch.device:
         _ext.ops()  # fail loudly if the native extension is missing on a GPU box
         return torch.device("cuda", gpu)
     return torch.device("cpu")
+
+
+def _real_samples(loader):
+    """How many of the samples ``loader`` yields on this rank are real: a DistributedSampler pads
+    the index list by wrapping to a multiple of the world size, and rank r takes positions r, r + W,
+    ... of it, so its positions >= n -- the tail of what it yields -- repeat early samples.  None:
+    no padding (no sampler, or drop_last)."""
+    s = getattr(loader, "sampler", None)
+    if s is None or not hasattr(s, "num_replicas") or getattr(s, "drop_last", False):
+        return None
+    return max(0, math.ceil((s.n - s.rank) / s.num_replicas))
+
+
+def evaluate(model, loader, device, group=None) -> dict:
+    """Loss and accuracy of ``model`` over ``loader`` in eval mode under ``no_grad``:
+    ``{"eval_loss": mean cross-entropy per sample, "eval_accuracy": correct / samples,
+    "eval_samples", "eval_images_per_sec"}``, the same dict on every rank.
+
+    A DDP wrapper is unwrapped after its deferred updates landed; at world size > 1 rank 0's BN
+    buffers (the authoritative running statistics) are broadcast first.  Under an initialised
+    process group every rank evaluates its shard (a ``DistributedSampler(shuffle=False)`` over the
+    test split; the padded tail is dropped, so every sample counts once) and the sums are added with
+    one all-reduce.  On the GPU the per-batch metrics are one small launch into a device accumulator
+    (``ops.eval_metrics``) read once at the end -- no host synchronisation per batch; eval-mode
+    ``no_grad`` GPU forwards run the fused inference plan unless the model's mode is ``layers``."""
+    device = torch.device(device)
+    world = tdist.get_world_size(group) if tdist.is_initialized() else 1
+    module = model
+    if isinstance(model, DistributedDataParallel):
+        model.wait_pending_updates()
+        module = model.module
+        if model.world_size > 1:
+            model._broadcast_buffers_now()  # rank 0's running statistics (the wrapper's C6 broadcast), once
+    on_gpu = device.type == "cuda"
+    limit = _real_samples(loader)
+    was_training = module.training
+    module.eval()
+    try:
+        with torch.no_grad():
+            if on_gpu:
+                acc = torch.zeros(3, dtype=torch.int64, device=device)  # [fp64 loss sum bits, correct, samples]
+                torch.cuda.synchronize(device)
+            else:
+                sums = torch.zeros(3, dtype=torch.float64)
+            t0 = time.perf_counter()
+            seen = 0
+            for images, labels in loader:
+                if limit is not None:
+                    if seen >= limit:
+                        break
+                    if seen + images.shape[0] > limit:
+                        images, labels = images[: limit - seen], labels[: limit - seen]
+                seen += images.shape[0]
+                logits = module(images)
+                if on_gpu:
+                    _ext.ops().eval_metrics(logits.float().contiguous(), labels.contiguous(), acc)
+                else:
+                    sums[0] += torch.nn.functional.cross_entropy(logits.double(), labels, reduction="sum")
+                    sums[1] += (logits.argmax(dim=1) == labels).sum()
+                    sums[2] += labels.numel()
+            if on_gpu:
+                torch.cuda.synchronize(device)  # the evaluation's one wait for the device
+                sums = torch.cat([acc[:1].view(torch.float64), acc[1:].to(torch.float64)])
+            dt = time.perf_counter() - t0
+            # this rank's wall time rides along, so every rank reports the same rate (the ranks' mean time)
+            sums = torch.cat([sums, torch.tensor([dt], dtype=torch.float64, device=sums.device)])
+            if world > 1:
+                tdist.all_reduce(sums, tdist.ReduceOp.SUM, group=group)
+            loss_sum, correct, count, dt = sums.tolist()
+            dt /= world
+    finally:
+        module.train(was_training)
+    count = int(count)
+    return {"eval_loss": loss_sum / count if count else float("nan"),
+            "eval_accuracy": correct / count if count else float("nan"),
+            "eval_samples": count,
+            "eval_images_per_sec": count / dt if dt > 0 else float("nan")}
 
 
 def train(gpu: int, args, distributed: bool = False) -> dict:
@@ -197,8 +282,20 @@ def train(gpu: int, args, distributed: bool = False) -> dict:
         summary["peak_mem_gb"] = torch.cuda.max_memory_allocated(device) / 1e9
     if getattr(args, "phase_times", False):
         summary["phases"] = timer.summary()
+    took = datetime.now() - start
+    ev = None
+    if getattr(args, "eval_size", 0) > 0:
+        test = SyntheticMNIST(size=args.eval_size, split="test")
+        tsampler = DistributedSampler(len(test), num_replicas=world, rank=rank, shuffle=False) if distributed else None
+        tloader = DeviceUpsampleLoader(test, getattr(args, "eval_batch_size", None) or batch_size, (H, W), device,
+                                       sampler=tsampler, levels=levels)
+        ev = evaluate(model, tloader, device)
+        summary.update(ev)
     if gpu == 0:
-        print("Training complete in: " + str(datetime.now() - start), flush=True)
+        print("Training complete in: " + str(took), flush=True)
+        if ev is not None:
+            print("Test Accuracy: {:.2f} %, Test Loss: {:.4f} ({} images)".format(
+                100.0 * ev["eval_accuracy"], ev["eval_loss"], ev["eval_samples"]), flush=True)
         if args.json:
             print(json.dumps(summary), flush=True)
     if args.checkpoint:
