@@ -60,24 +60,98 @@ static_assert(F2_WG * F2_LDS <= 160 * 1024, "workgroups per CU");
 // 16 zero bytes: the DMA source of staged records outside the image
 __device__ __attribute__((aligned(16))) uint32_t g_f2_zero[4] = {0u, 0u, 0u, 0u};
 
+// One tile of a workgroup's list, all wave-uniform (SGPRs): decoded once from its table entry and
+// carried next -> current -> previous through the tile loop.  full: the tile lies inside the image,
+// so its statistics, its y2h / ya / a2 stores run unmasked (all but ~1 % of the tiles).
 struct F2Tile {
   int b, r0, c0;
+  bool full;
 };
 
+__device__ __forceinline__ F2Tile f2_tile(int entry, int P) {  // entry: conv2_common.h tile order
+  F2Tile x;
+  x.b = entry >> 24;
+  x.r0 = ((entry >> 12) & 4095) * F2_TH;
+  x.c0 = (entry & 4095) * F2_TC;
+  x.full = x.r0 + F2_TH <= P && x.c0 + F2_TC <= P;
+  return x;
+}
+
+// A thread's share of the per-tile addresses.  None of it depends on the tile, so it is computed
+// once before the tile loop; a tile then only forms scalar 64-bit bases (f2_dma, f2_store,
+// f2_store_ya, f2_store_a2) and interior tiles add the two with no bounds arithmetic.
+struct F2Lane {
+  uint32_t dma[F2_DMA_PER_WAVE];  // B from the staged window's first record (0: no record)
+  uint32_t st_lds, st_glb;  // f2_store: the thread's staged chunk, B from the tile's first y2h pixel
+  uint32_t ya_lds;          // f2_store_ya: the thread's staged pooled chunk (words)
+  int64_t ya_glb;           //   halves from the tile's block of channel 0
+  uint32_t a2_glb;          // f2_store_a2: B from the tile's first window
+};
+
+constexpr uint64_t F2_QPX = 0xfeab6732dc894510ull;  // nibble quad -> px (f2_store)
+__device__ __forceinline__ int f2_stage_off(int row, int px, int chunk);
+__device__ __forceinline__ int f2_ystage_off(int co, int e);
+
+template <int WV>
+__device__ __forceinline__ F2Lane f2_lane(int P, const PBGeom& pg, int lane) {
+  F2Lane L;
+#pragma unroll
+  for (int j = 0; j < F2_DMA_PER_WAVE; ++j) {
+    const int px = (WV * F2_DMA_PER_WAVE + j) * 32 + (lane >> 1), half = lane & 1;
+    const int rr = px / F2_SC, cc = px - rr * F2_SC;
+    // (records 240 .. 255 of the plane are never read: on an interior tile their lanes fetch the
+    // window's first record instead of the zero source, with no select)
+    L.dma[j] = px < F2_REC ? (uint32_t)((rr * P + cc) * 32 + half * 16) : 0u;
+  }
+  // f2_store: thread e, i -> chunk q = e + 256 i of [row 8][px 16][c8 4]: row = WV + 4 i
+  const int qpx = (int)((F2_QPX >> (4 * (lane >> 2))) & 15u), c8 = lane & 3;
+  L.st_lds = (uint32_t)f2_stage_off(WV, qpx, c8);
+  L.st_glb = (uint32_t)((WV * P + qpx) * 64 + c8 * 16);
+  // f2_store_ya: thread e -> channel e / 8, 4 values e % 8
+  const int co = WV * 8 + (lane >> 3), part = lane & 7;
+  L.ya_lds = (uint32_t)f2_ystage_off(co, part * 4);
+  L.ya_glb = (int64_t)co * pg.Q4 * pg.Q8 * 32 + part * 4;
+  // f2_store_a2: thread e < 32 -> window (e / 8, e % 8)
+  L.a2_glb = (uint32_t)(((lane >> 3) * (P >> 1) + (lane & 7)) * 8);
+  return L;
+}
+
 template <int DIAG, int WV>
-__device__ __forceinline__ void f2_dma(const uint4* __restrict__ p1, const F2Tile& x, int P, char* buf, int lane) {
+__device__ __forceinline__ void f2_dma(const uint4* __restrict__ p1, const F2Tile& x, int P, char* buf, int lane,
+                                       const F2Lane& L) {
   if constexpr (DIAG == 3) return;
-  const char* base = reinterpret_cast<const char*>(p1) + (((int64_t)x.b * P + x.r0 - 2) * P + (x.c0 - 2)) * 32;
+  // (image rows fit 32 bits -- B <= 255, <= 4095 tiles per side -- so one 32 x 32 -> 64-bit scalar
+  // multiply forms the base, here and in the stores)
+  const char* base = reinterpret_cast<const char*>(p1) + ((int64_t)(x.b * P + x.r0 - 2) * P + (x.c0 - 2)) * 32;
+  // the whole 12 x 20 window inside the image (tile-uniform): no per-lane bounds, no zero source
+  if (x.r0 >= 2 && x.c0 >= 2 && x.r0 + F2_TH + 2 <= P && x.c0 + F2_TC + 2 <= P) {
+#pragma unroll
+    for (int j = 0; j < F2_DMA_PER_WAVE; ++j)
+      __builtin_amdgcn_global_load_lds(base + L.dma[j],
+                                       (__attribute__((address_space(3))) void*)(buf + (WV * F2_DMA_PER_WAVE + j) * 1024),
+                                       16, 0, 0);
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < F2_DMA_PER_WAVE; ++j) {
     const int rg = WV * F2_DMA_PER_WAVE + j;
-    const int px = rg * 32 + (lane >> 1), half = lane & 1;
+    const int px = rg * 32 + (lane >> 1);
     const int rr = px / F2_SC, cc = px - rr * F2_SC;
     const int gr = x.r0 - 2 + rr, gc = x.c0 - 2 + cc;
     const bool ok = px < F2_REC && gr >= 0 && gr < P && gc >= 0 && gc < P;
-    const char* src = ok ? base + ((int64_t)rr * P + cc) * 32 + half * 16 : reinterpret_cast<const char*>(g_f2_zero);
+    const char* src = ok ? base + L.dma[j] : reinterpret_cast<const char*>(g_f2_zero);
     __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(buf + rg * 1024), 16, 0, 0);
   }
+}
+
+// The tile boundary: every wave's LDS-DMA loads of the tile about to be computed have landed, then
+// the workgroup meets.  The vmcnt(0) is stated here because nothing else guarantees it: the
+// workgroup-scope fence of __syncthreads() waits for LDS traffic only, and the compiler's own
+// vmcnt(0) in front of the barrier is a by-product of its counter tracking that came and went with
+// unrelated changes to the loop (without it the MFMAs can read a plane the DMA is still writing).
+__device__ __forceinline__ void f2_tile_barrier() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
 }
 
 // One wave's MFMAs for one tile: rows 4RH .. 4RH+3 of the tile, co half NT (weights in W).
@@ -169,11 +243,6 @@ __device__ __forceinline__ void f2_stage(const f32x4 (&acc)[4], const F2Tile& x,
   const int li = lane & 15, g = lane >> 4;
   const int co = 16 * NT + li;
   float ymf = 0.f;
-  uint32_t h[4][4];  // y2h bits (conv2_common.h)
-#pragma unroll
-  for (int o = 0; o < 4; ++o)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) h[o][r] = f16_bits(acc[o][r] * ksc);
   // acc = (y2 - b2) / inv: statistics shifted by the bias, scaled at the end
 #pragma unroll
   for (int o = 0; o < 4; ++o) {
@@ -232,52 +301,70 @@ __device__ __forceinline__ void f2_stage(const f32x4 (&acc)[4], const F2Tile& x,
     // pcols 2g, 2g+1 are adjacent words of one swizzled chunk: one ds_write_b64
     *reinterpret_cast<uint2*>(ystage + f2_ystage_off(co, (2 * RH + i) * 8 + 2 * g)) = make_uint2(e[0], e[1]);
   }
-  // lane li = 0 of group g stages the 4 windows (2RH + i, 2g + j) in LDS after the pooled block
-  // (word = bits 16g .. 16g+15 of each code-bit ballot: channels 16NT + 0..15); f2_store_a2 writes
-  // the tile's 32 windows as 4 rows of 64 B
+  // The wave's 16 a2 words (window (2RH + i, 2g + j), sl = 2i + j: bits 16g .. 16g+15 of both
+  // code-bit ballots, channels 16NT + 0..15) are staged in LDS after the pooled block; f2_store_a2
+  // writes the tile's 32 windows as 4 rows of 64 B.  The ballots are scalars: each word is packed on
+  // the scalar unit and dropped into lane 4 sl + g of one register (v_writelane), and lanes 0-15
+  // write it with one ds_write_b32.  (Lane 16g picking its 32-bit half and 16 bits of it per lane
+  // cost a v_mov and a v_cndmask per ballot half: 30 VALU per tile.)
   {
     uint32_t* ab = reinterpret_cast<uint32_t*>(ystage + 32 * 32);
-    // group g's 16 bits of each ballot: the 32-bit half (g >= 2: upper), then one byte permute takes
-    // bits 16(g & 1) .. +15 of both code-bit words (a 64-bit shift by the per-lane 16g cost ~9 VALU a window)
-    const bool upper = g >= 2;
-    const uint32_t psel = (g & 1) ? 0x07060302u : 0x05040100u;
-    if (li == 0) {
+    uint32_t word = 0u;
 #pragma unroll
-      for (int sl = 0; sl < 4; ++sl) {
-        const uint32_t w0 = upper ? (uint32_t)(cb0[sl] >> 32) : (uint32_t)cb0[sl];
-        const uint32_t w1 = upper ? (uint32_t)(cb1[sl] >> 32) : (uint32_t)cb1[sl];
-        ab[((2 * RH + (sl >> 1)) * 8 + 2 * g + (sl & 1)) * 2 + NT] = __builtin_amdgcn_perm(w1, w0, psel);
+    for (int sl = 0; sl < 4; ++sl)
+#pragma unroll
+      for (int gg = 0; gg < 4; ++gg) {
+        const uint32_t w0 = (uint32_t)(cb0[sl] >> (32 * (gg >> 1))), w1 = (uint32_t)(cb1[sl] >> (32 * (gg >> 1)));
+        uint32_t wd;  // bits 16 (gg & 1) .. +15 of w0 | the same of w1 << 16
+        if (gg & 1) asm("s_pack_hh_b32_b16 %0, %1, %2" : "=s"(wd) : "s"(w0), "s"(w1));
+        else asm("s_pack_ll_b32_b16 %0, %1, %2" : "=s"(wd) : "s"(w0), "s"(w1));
+        // (an immediate lane select: no SGPR lane-select hazard to wait for)
+        asm("v_writelane_b32 %0, %1, %2" : "+v"(word) : "s"(wd), "n"(4 * sl + gg));
       }
-    }
+    const int sl = (lane >> 2) & 3, gg = lane & 3;
+    if (lane < 16) ab[((2 * RH + (sl >> 1)) * 8 + 2 * gg + (sl & 1)) * 2 + NT] = word;
   }
-  // the y2h values: every lane writes its channel's half-word (no cross-lane pairing: the DPP move
-  // and the pack cost 2 VALU per value)
+}
+
+// the tile's y2h values (y2h bits, conv2_common.h): every lane writes its channel's half-word (no
+// cross-lane pairing: the DPP move and the pack cost 2 VALU per value).  The same for every kind of
+// tile, so it runs before f2_run's branch into f2_stage: as the common tail of the three
+// instantiations the compiler merged it and paid 12 v_mov per tile to bring the accumulators
+// to the merged block's registers.
+__device__ __forceinline__ void f2_stage_y2h(const f32x4 (&acc)[4], char* stage, int RH, int NT, int lane, float ksc) {
+  const int li = lane & 15, g = lane >> 4;
+  const int co = 16 * NT + li;
 #pragma unroll
   for (int o = 0; o < 4; ++o)
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       *reinterpret_cast<unsigned short*>(stage + (((4 * RH + o) * F2_TC + 4 * g + r) * F2_PXREC) + co * 2) =
-          (unsigned short)h[o][r];
+          (unsigned short)f16_bits(acc[o][r] * ksc);
 }
 
 // the workgroup stores the staged pooled block: thread e -> channel e / 8, 4 values (8 B) e % 8
+// (F2Lane: ya_lds, ya_glb), over the scalar base of the tile's pooled block in channel 0
 __device__ __forceinline__ void f2_store_ya(const float* ystage, const F2Tile& x, unsigned short* __restrict__ ya,
-                                            const PBGeom& pg) {
+                                            const PBGeom& pg, const F2Lane& L) {
   const int tr = x.r0 / F2_TH, tc = x.c0 / F2_TC;  // = the tile's pooled block
   if (tr >= pg.Q4 || tc >= pg.Q8) return;          // (odd P: a last tile row beyond the pooled image)
-  const int e = threadIdx.x, co = e >> 3, part = e & 7;
-  const uint4 v = *reinterpret_cast<const uint4*>(ystage + f2_ystage_off(co, part * 4));
-  st_stream(reinterpret_cast<uint2*>(ya + ((((int64_t)x.b * 32 + co) * pg.Q4 + tr) * pg.Q8 + tc) * 32 + part * 4),
+  unsigned short* base = ya + ((int64_t)(x.b * 32 * pg.Q4 + tr) * pg.Q8 + tc) * 32;
+  const uint4 v = *reinterpret_cast<const uint4*>(ystage + L.ya_lds);
+  st_stream(reinterpret_cast<uint2*>(base + L.ya_glb),
             make_uint2(__builtin_amdgcn_perm(v.y, v.x, 0x05040100u), __builtin_amdgcn_perm(v.w, v.z, 0x05040100u)));
 }
 
-// the tile's 32 pooling windows' argmax words (a2, conv2_common.h): thread e < 32 -> window e
-__device__ __forceinline__ void f2_store_a2(const float* ystage, const F2Tile& x, uint32_t* __restrict__ a2, int P) {
-  const int e = threadIdx.x, Q = P >> 1;
-  const int py = (x.r0 >> 1) + (e >> 3), px = (x.c0 >> 1) + (e & 7);
-  if (e < 32 && py < Q && px < Q)  // (non-temporal, as y2h: dirty lines left to the head forward cost it ~5 us)
-    st_stream(reinterpret_cast<uint2*>(a2 + (((int64_t)x.b * Q + py) * Q + px) * 2),
-              reinterpret_cast<const uint2*>(ystage + 32 * 32)[e]);
+// the tile's 32 pooling windows' argmax words (a2, conv2_common.h): thread e < 32 (wave 0) -> window e
+template <int WV>
+__device__ __forceinline__ void f2_store_a2(const float* ystage, const F2Tile& x, uint32_t* __restrict__ a2, int P,
+                                            int lane, const F2Lane& L) {
+  if constexpr (WV != 0) return;
+  const int Q = P >> 1;
+  char* base = reinterpret_cast<char*>(a2) + ((int64_t)(x.b * Q + (x.r0 >> 1)) * Q + (x.c0 >> 1)) * 8;
+  bool ok = lane < 32;
+  if (!x.full) ok = ok && (x.r0 >> 1) + (lane >> 3) < Q && (x.c0 >> 1) + (lane & 7) < Q;
+  if (ok)  // (non-temporal, as y2h: dirty lines left to the head forward cost it ~5 us)
+    st_stream(reinterpret_cast<uint2*>(base + L.a2_glb), reinterpret_cast<const uint2*>(ystage + 32 * 32)[lane]);
 }
 
 // the whole workgroup stores a staged tile as y2h: thread e, i -> 8 channels q = e + 256 i of
@@ -285,21 +372,28 @@ __device__ __forceinline__ void f2_store_a2(const float* ystage, const F2Tile& x
 // 1 KiB, 16 pixels of one row.  H16: lane quad -> pixel through F2_QPX, so each 16-lane bank
 // group of ds_read_b128 ({0-3,12-15,20-27}, ...) reads pixels p, p+4, p+8, p+12, whose 80-B
 // records start 0, 64, 128, 192 B apart mod 256 -- conflict-free (quad = pixel read 3-way).
-constexpr uint64_t F2_QPX = 0xfeab6732dc894510ull;  // nibble quad -> px
-template <int DIAG>
-__device__ __forceinline__ void f2_store(const char* stage, const F2Tile& x, unsigned short* __restrict__ y2h, int P) {
+// A thread's two chunks sit 4 image rows apart: one 32-bit offset (F2Lane: st_lds, st_glb) over
+// the scalar 64-bit base of the tile's first pixel (64-bit: y2h passes 2 GiB), a scalar row stride.
+template <int DIAG, int WV>
+__device__ __forceinline__ void f2_store(const char* stage, const F2Tile& x, unsigned short* __restrict__ y2h, int P,
+                                         int lane, const F2Lane& L) {
   if constexpr (DIAG == 4) return;  // timing-only: no y2h
-  const int e = threadIdx.x;
-  const int qpx = (int)((F2_QPX >> (4 * ((e >> 2) & 15))) & 15u);
+  constexpr int N = F2_TH * F2_TC * 4 / F2_THREADS, LROW = 4 * F2_TC * F2_PXREC;
+  char* base = reinterpret_cast<char*>(y2h) + ((int64_t)(x.b * P + x.r0) * P + x.c0) * 64;
+  const int64_t rs = (int64_t)P * (4 * 64);
+  const char* src = stage + L.st_lds;
+  if (x.full) {
 #pragma unroll
-  for (int i = 0; i < F2_TH * F2_TC * 4 / F2_THREADS; ++i) {
-    const int q = e + F2_THREADS * i;
-    const int row = q >> 6, px = qpx, c8 = q & 3;
-    const int gr = x.r0 + row, gc = x.c0 + px;
-    const uint4 v = *reinterpret_cast<const uint4*>(stage + f2_stage_off(row, px, c8));
-    if (gr < P && gc < P)
-      st_stream(reinterpret_cast<float4*>(y2h + (((int64_t)x.b * P + gr) * P + gc) * 32 + c8 * 8),
-                __builtin_bit_cast(float4, v));
+    for (int i = 0; i < N; ++i)
+      st_stream(reinterpret_cast<float4*>(base + i * rs + L.st_glb),
+                __builtin_bit_cast(float4, *reinterpret_cast<const uint4*>(src + i * LROW)));
+    return;
+  }
+  const bool cok = x.c0 + (int)((F2_QPX >> (4 * (lane >> 2))) & 15u) < P;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const uint4 v = *reinterpret_cast<const uint4*>(src + i * LROW);
+    if (x.r0 + WV + 4 * i < P && cok) st_stream(reinterpret_cast<float4*>(base + i * rs + L.st_glb), __builtin_bit_cast(float4, v));
   }
 }
 
@@ -319,14 +413,6 @@ __device__ __forceinline__ void f2_run(const uint4* __restrict__ p1, const uint4
   // work index t = w + kk * grid at mine[kk * sk]: the table is per workgroup (fused_ops.cpp
   // tile_order, sw = ceil(total / grid), sk = 1), so consecutive tiles share a scalar-cache line
   const int* __restrict__ mine = order + w * sw;
-  auto decode = [&](int kk) {
-    F2Tile x;
-    int tr, tc;
-    tile_from_order(mine, kk * sk, x.b, tr, tc);
-    x.r0 = tr * F2_TH;
-    x.c0 = tc * F2_TC;
-    return x;
-  };
   // weights: fwd pack wp[s][nt][g][co16][j8] -> uint4 index (s * 2 + nt) * 64 + lane (conv2_pack.hip)
   f32x4 W[13];
 #pragma unroll
@@ -347,27 +433,40 @@ __device__ __forceinline__ void f2_run(const uint4* __restrict__ p1, const uint4
   double s_d = 0.0, q_d = 0.0;
   uint32_t ymx = 0u;
   f32x4 acc[4];
-  F2Tile prev{0, 0, 0};
+  const F2Lane L = f2_lane<WV>(P, pg, lane);
+  // one table entry per tile: the look-ahead entry is loaded before the barrier (its wait falls
+  // there), decoded once, and carried nx -> cur -> prev
+  F2Tile nx{0, 0, 0, false}, prev{0, 0, 0, false};
   bool have_prev = false;
   int t = w;
-  if (t < total) f2_dma<DIAG, WV>(p1, decode(0), P, smem, lane);
+  if (t < total) {
+    nx = f2_tile(mine[0], P);
+    f2_dma<DIAG, WV>(p1, nx, P, smem, lane, L);
+  }
   int kk = 0;
   for (; t < total; t += gridDim.x, ++kk) {
-    const F2Tile cur = decode(kk);
+    const F2Tile cur = nx;
+    const bool more = t + (int)gridDim.x < total;
+    const int ahead = mine[(more ? kk + 1 : kk) * sk];
     // tile t's DMA landed (vmcnt(0) + barrier); p1 buffer (kk+1)&1 is free; the staged
     // tile t-1 (stage (kk+1)&1) is complete
-    __syncthreads();
-    if (t + (int)gridDim.x < total) f2_dma<DIAG, WV>(p1, decode(kk + 1), P, smem + ((kk + 1) & 1) * F2_PBUF, lane);
+    f2_tile_barrier();
+    asm volatile("" ::"s"(ahead));  // (consumed here: the load stays above the barrier and is not sunk into the branch)
+    if (more) {
+      nx = f2_tile(ahead, P);
+      f2_dma<DIAG, WV>(p1, nx, P, smem + ((kk + 1) & 1) * F2_PBUF, lane, L);
+    }
     if (have_prev) {
-      f2_store<DIAG>(smem + F2_OFF_S + ((kk + 1) & 1) * F2_STAGE, prev, y2, P);
-      f2_store_ya(ys + ((kk + 1) & 1) * (F2_YSTAGE / 4), prev, ya, pg);
-      f2_store_a2(ys + ((kk + 1) & 1) * (F2_YSTAGE / 4), prev, a2, P);
+      f2_store<DIAG, WV>(smem + F2_OFF_S + ((kk + 1) & 1) * F2_STAGE, prev, y2, P, lane, L);
+      f2_store_ya(ys + ((kk + 1) & 1) * (F2_YSTAGE / 4), prev, ya, pg, L);
+      f2_store_a2<WV>(ys + ((kk + 1) & 1) * (F2_YSTAGE / 4), prev, a2, P, lane, L);
     }
     f2_compute<DIAG>(smem + (kk & 1) * F2_PBUF, W, acc, RH, lane);
-    if (cur.r0 + F2_TH <= P && cur.c0 + F2_TC <= P && plain)  // tile- and wave-uniform
+    f2_stage_y2h(acc, smem + F2_OFF_S + (kk & 1) * F2_STAGE, RH, NT, lane, ksc);
+    if (cur.full && plain)  // tile- and wave-uniform
       f2_stage<false, true>(acc, cur, smem + F2_OFF_S + (kk & 1) * F2_STAGE, ys + (kk & 1) * (F2_YSTAGE / 4), P, RH, NT,
                             lane, bco, inv, ksc, neg, zg, s_acc, q_acc, ymx, a2);
-    else if (cur.r0 + F2_TH <= P && cur.c0 + F2_TC <= P)
+    else if (cur.full)
       f2_stage<false, false>(acc, cur, smem + F2_OFF_S + (kk & 1) * F2_STAGE, ys + (kk & 1) * (F2_YSTAGE / 4), P, RH, NT, lane,
                       bco, inv, ksc, neg, zg, s_acc, q_acc, ymx, a2);
     else
@@ -382,9 +481,9 @@ __device__ __forceinline__ void f2_run(const uint4* __restrict__ p1, const uint4
   }
   __syncthreads();
   if (have_prev) {
-    f2_store<DIAG>(smem + F2_OFF_S + ((kk - 1) & 1) * F2_STAGE, prev, y2, P);
-    f2_store_ya(ys + ((kk - 1) & 1) * (F2_YSTAGE / 4), prev, ya, pg);
-    f2_store_a2(ys + ((kk - 1) & 1) * (F2_YSTAGE / 4), prev, a2, P);
+    f2_store<DIAG, WV>(smem + F2_OFF_S + ((kk - 1) & 1) * F2_STAGE, prev, y2, P, lane, L);
+    f2_store_ya(ys + ((kk - 1) & 1) * (F2_YSTAGE / 4), prev, ya, pg, L);
+    f2_store_a2<WV>(ys + ((kk - 1) & 1) * (F2_YSTAGE / 4), prev, a2, P, lane, L);
   }
   // max |acc| of channel 16NT + li over the 4 lane groups (then the two waves of this co half)
   ymx = max(ymx, (uint32_t)__shfl_xor((int)ymx, 16, 64));
@@ -548,14 +647,6 @@ __device__ __forceinline__ void f2i_run(const uint4* __restrict__ p1, const uint
   const int total = tiles_c * tiles_r * B;
   const int w = xcd_remap(blockIdx.x, gridDim.x);
   const int* __restrict__ mine = order + w * sw;
-  auto decode = [&](int kk) {
-    F2Tile x;
-    int tr, tc;
-    tile_from_order(mine, kk * sk, x.b, tr, tc);
-    x.r0 = tr * F2_TH;
-    x.c0 = tc * F2_TC;
-    return x;
-  };
   f32x4 W[13];
 #pragma unroll
   for (int s = 0; s < 13; ++s) W[s] = __builtin_bit_cast(f32x4, wpack[(s * 2 + NT) * 64 + lane]);
@@ -566,17 +657,27 @@ __device__ __forceinline__ void f2i_run(const uint4* __restrict__ p1, const uint
   const PBGeom pg = pb_geom(P / 2);
   float* ys = reinterpret_cast<float*>(smem + F2I_OFF_Y);
   f32x4 acc[4];
-  F2Tile prev{0, 0, 0};
+  const F2Lane L = f2_lane<WV>(P, pg, lane);
+  F2Tile nx{0, 0, 0, false}, prev{0, 0, 0, false};  // (one decode per tile, as f2_run)
   bool have_prev = false;
   int t = w;
-  if (t < total) f2_dma<0, WV>(p1, decode(0), P, smem, lane);
+  if (t < total) {
+    nx = f2_tile(mine[0], P);
+    f2_dma<0, WV>(p1, nx, P, smem, lane, L);
+  }
   int kk = 0;
   for (; t < total; t += gridDim.x, ++kk) {
-    const F2Tile cur = decode(kk);
+    const F2Tile cur = nx;
+    const bool more = t + (int)gridDim.x < total;
+    const int ahead = mine[(more ? kk + 1 : kk) * sk];
     // tile t's DMA landed; p1 buffer (kk+1)&1 is free; the pooled block of tile t-1 is staged
-    __syncthreads();
-    if (t + (int)gridDim.x < total) f2_dma<0, WV>(p1, decode(kk + 1), P, smem + ((kk + 1) & 1) * F2_PBUF, lane);
-    if (have_prev) f2_store_ya(ys + ((kk + 1) & 1) * (F2I_YSTAGE / 4), prev, ya, pg);
+    f2_tile_barrier();
+    asm volatile("" ::"s"(ahead));  // (as f2_run)
+    if (more) {
+      nx = f2_tile(ahead, P);
+      f2_dma<0, WV>(p1, nx, P, smem + ((kk + 1) & 1) * F2_PBUF, lane, L);
+    }
+    if (have_prev) f2_store_ya(ys + ((kk + 1) & 1) * (F2I_YSTAGE / 4), prev, ya, pg, L);
     f2_compute<0>(smem + (kk & 1) * F2_PBUF, W, acc, RH, lane);
     if (plain)  // wave-uniform
       f2i_pool<true>(acc, ys + (kk & 1) * (F2I_YSTAGE / 4), RH, NT, lane, ksc, neg, zg);
@@ -586,7 +687,7 @@ __device__ __forceinline__ void f2i_run(const uint4* __restrict__ p1, const uint
     have_prev = true;
   }
   __syncthreads();
-  if (have_prev) f2_store_ya(ys + ((kk - 1) & 1) * (F2I_YSTAGE / 4), prev, ya, pg);
+  if (have_prev) f2_store_ya(ys + ((kk - 1) & 1) * (F2I_YSTAGE / 4), prev, ya, pg, L);
 }
 
 __global__ __launch_bounds__(F2_THREADS, F2_WG) void conv2_fwd2_inference_kernel(
