@@ -27,6 +27,42 @@ def test_plane_shards_cover_and_balance(world):
     assert shards == factored.plane_shards(world, planes=32)
 
 
+@pytest.mark.parametrize("groups", range(1, 41))
+@pytest.mark.parametrize("per", [361, 4225, 4096])
+def test_column_groups_are_ranges_the_head_launch_takes(groups, per):
+    """The grouped activation exchange's column groups of 32 planes of ``per`` columns (pooled edges
+    19, 65 and 64): contiguous, non-empty, covering; the head's range launch (head_pb.hip
+    tds_head_fwd_pb) takes [c0, c1) only when c0 * per and (c1 - c0) * per are multiples of 4, so odd
+    planes are cut at multiples of 4 channels; planes that are a multiple of 4 keep the plain
+    round(i * 32 / n) cuts."""
+    in_f = 32 * per
+    ex = factored.ActivationExchange(torch.nn.Parameter(torch.zeros(1, 1)), None, None, 2, "activations",
+                                     lambda on: None, lambda: None, None, groups=groups, source="rows")
+    got = ex.column_groups(in_f, planes=32)
+    assert got[0][0] == 0 and got[-1][1] == in_f
+    assert all(got[i][1] == got[i + 1][0] for i in range(len(got) - 1))
+    assert all(k1 > k0 for k0, k1 in got)
+    assert all(k0 % per == 0 and k1 % per == 0 for k0, k1 in got)  # whole planes
+    for k0, k1 in got:  # the launch's own rule
+        assert k0 % 4 == 0 and (k1 - k0) % 4 == 0, (k0, k1)
+    if per % 4:
+        assert all(k0 % (4 * per) == 0 and (k1 - k0) % (4 * per) == 0 for k0, k1 in got)
+        assert len(got) == min(groups, 8)
+    else:
+        n = min(groups, 32)
+        cuts = [round(i * 32 / n) for i in range(n + 1)]
+        assert got == [(cuts[i] * per, cuts[i + 1] * per) for i in range(n) if cuts[i + 1] > cuts[i]]
+    if groups in (1, 2, 4, 8):  # these never needed another cut: the same groups at every plane size
+        assert [(k0 // per, k1 // per) for k0, k1 in got] == [(i * 32 // groups, (i + 1) * 32 // groups)
+                                                              for i in range(groups)]
+    # column_chunks (the head backward takes any range) keeps the plain cuts
+    ex.chunks = groups
+    n = min(groups, 32)
+    cuts = [round(i * 32 / n) for i in range(n + 1)]
+    assert ex.column_chunks(in_f, planes=32) == [(cuts[i] * per, cuts[i + 1] * per) for i in range(n)
+                                                 if cuts[i + 1] > cuts[i]]
+
+
 def test_source_values_and_cpu_weight():
     w = torch.nn.Parameter(torch.zeros(10, 32 * 64 * 64))
     ex = _exchange(w, 2, "sharded", "pooled-sharded")

@@ -636,9 +636,17 @@ std::tuple<Tensor, Tensor, Tensor> fused_head_forward_aff_ce(const Tensor& ya, c
 // dlogits, loss, 1/count) -- and fused_head_forward_range runs channels [c0, c1) over it, writing
 // that range's X rows into x_out [B, (c1-c0)*Q*Q]; the launch that completes the 32nd channel
 // finishes the logits (and, with labels, the cross-entropy) inside itself (head_pb.hip HPFin).
+// head_forward_range_ws opens the sequence: it also zeroes the head forward's counters on ya's
+// stream, so a sequence abandoned midway (an exception between two ranges) cannot make the next
+// one finish its logits early.
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> head_forward_range_ws(const Tensor& ya, const Tensor& wfc,
                                                                                  int64_t P) {
+  TORCH_CHECK(ya.is_cuda() && ya.dim() == 3 && wfc.dim() == 2,
+              "head_forward_range_ws: ya [B,32,PB] on the GPU, fc.weight [NC,K]");
   const int64_t B = ya.size(0), Q = P / 2, NC = wfc.size(0);
+  c10::DeviceGuard guard(ya.device());
+  TORCH_CHECK(tds_head_fwd_range_begin(stream_of(ya)) == 0,
+              "head_forward_range_ws: could not reset the head forward's counters");
   const int nblk = 32 * tds_head_pb_nblk((int)Q);
   auto o = ya.options().dtype(at::kFloat);
   return {at::empty({(int64_t)(nblk + 32) * B * NC}, o.dtype(at::kDouble)), at::empty({B * NC}, o.dtype(at::kDouble)),

@@ -976,6 +976,17 @@ int tds_head_fwd_pb(const unsigned short* ya, TdsYaDec yd, const float* Wfc, con
   return 0;
 }
 
+// A range sequence's channels counter (sync[32]) is reset only by the launch that draws the 32nd
+// channel: a sequence that stopped early (an exception between two ranges) leaves it stale, and the
+// next one on the stream would finish its logits after too few channels.  The caller that opens a
+// sequence zeroes the site's counters on the stream first; the whole launch needs none of this (it
+// always draws all 32).
+int tds_head_fwd_range_begin(hipStream_t st) {
+  uint32_t* sync = tds_sync_words(kSyncHeadFwd, st);
+  if (sync == nullptr) return -1;
+  return hipMemsetAsync(sync, 0, 33 * sizeof(uint32_t), st) == hipSuccess ? 0 : -1;
+}
+
 // partial: double [32][npass * nblk][2], npass = ceil(B / 8)
 int tds_head_bwd_pb_npass(int B) { return (B + HP_MAXB - 1) / HP_MAXB; }
 

@@ -229,6 +229,9 @@ int tds_head_fwd_pb(const unsigned short* ya, TdsYaDec yd, const float* Wfc, con
                     double* sums, float* logits, float* xout, int B, int Q, int NC, hipStream_t st,
                     bool fused_fin = true, const int64_t* labels = nullptr, float* dlogits = nullptr,
                     float* loss = nullptr, float* inv_count = nullptr, int c0 = 0, int c1 = 32);
+// Opens a step's sequence of channel-range forward launches on st: the head forward's 33 counters
+// zeroed on the stream (a sequence abandoned midway leaves the channels counter stale).  0 or -1.
+int tds_head_fwd_range_begin(hipStream_t st);
 int tds_head_bwd_pb_npass(int B);
 // The activation exchange's fc step from the all-gathered pooled inputs (head_pb.hip head_upd_pb_kernel):
 // ya_all [nranks][B][32][PB] fp16 (ya_rs elements per rank), rec [nranks][128] (tds_head_pooled_record),

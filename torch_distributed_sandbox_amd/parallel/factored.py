@@ -266,11 +266,19 @@ class ActivationExchange:
 
     def column_groups(self, in_f: int, planes: int = 0):
         """The [k0, k1) column ranges of the grouped activation exchange: ``groups`` ranges of whole
-        planes (the fused head: channels) or 64-aligned."""
+        planes (the fused head: channels) or 64-aligned.  The head's range launch stores a group's
+        rows 16 bytes at a time and so takes a range only when its first column and its width are
+        multiples of 4 (head_pb.hip tds_head_fwd_pb): planes of a size that is no multiple of 4 (an
+        odd pooled edge) are cut at multiples of 4 planes, which leaves at most planes / 4 groups."""
         if planes:
             per = in_f // planes
-            n = min(self.groups, planes)
-            cuts = [round(i * planes / n) for i in range(n + 1)]
+            if per % 4 and planes % 4 == 0:
+                quads = planes // 4
+                n = min(self.groups, quads)
+                cuts = [4 * round(i * quads / n) for i in range(n + 1)]
+            else:
+                n = min(self.groups, planes)
+                cuts = [round(i * planes / n) for i in range(n + 1)]
             return [(cuts[i] * per, cuts[i + 1] * per) for i in range(n) if cuts[i + 1] > cuts[i]]
         return [(a, e) for a, e in shard_bounds(in_f, self.groups) if e > a]
 
