@@ -517,6 +517,64 @@ def test_zero_suppressed_exchange_bitwise_equal(mode, backend, world, B):
                  timeout=300)
 
 
+def _w_step_record(rank, world, port, mode, compress):
+    """The exchange holds one record per exchanged step and none between steps: after every
+    backward -- accumulating under no_sync(), synced, and synced with a capacity below the counts
+    (the overflow's dense re-send) -- no record is left, ``active`` is None, ``steps_exchanged``
+    moved by exactly the synced steps and ``fc_grad_path()`` carries the path's tag."""
+    dist = _init(rank, world, port, "gloo")
+    from torch_distributed_sandbox_amd.models import ConvNet
+    from torch_distributed_sandbox_amd.ops import SGD, CrossEntropyLoss
+    from torch_distributed_sandbox_amd.parallel import DistributedDataParallel
+
+    torch.manual_seed(0)
+    # 232: the smallest ConvNet image whose fc layer (10 x 107648 >= 2^20 elements) DDP gives an
+    # exchange at all; a 64 x 64 image's fc layer (10 x 8192) takes the plain bucket all-reduce
+    H, B = 232, 2
+    assert not DistributedDataParallel(ConvNet(image_shape=(64, 64)), grad_exchange="activations").exchanges
+    m = ConvNet(image_shape=(H, H))
+    d = DistributedDataParallel(m, grad_exchange=mode, exchange_compress=compress,
+                                allreduce_chunks=3 if mode == "chunked" else None)
+    o = d.attach_optimizer(SGD(m.parameters(), 0.05))
+    crit = CrossEntropyLoss()
+    ex, = d.exchanges
+    tag = {"activations": "activation-exchange", "sharded": "sharded-exchange"}.get(mode)
+    tag = "chunked-allreduce" if tag is None else tag + ("(zs)" if compress else "")
+    g = torch.Generator().manual_seed(7)
+    xs = torch.rand(world, B, 1, H, H, generator=g)
+    ys = torch.randint(0, 10, (world, B), generator=g)
+    assert ex._step is None and ex.active is None and ex.steps_exchanged == 0
+
+    def backward(sync, what):
+        before = ex.steps_exchanged
+        if sync:
+            crit(d(xs[rank]), ys[rank]).backward()
+        else:
+            with d.no_sync():
+                crit(d(xs[rank]), ys[rank]).backward()
+        assert ex._step is None and ex.active is None, what
+        assert ex.steps_exchanged == before + (1 if sync else 0), what
+        # (before the first exchanged step the layer's gradient has only met the plain path)
+        assert d.fc_grad_path() == (tag if ex.steps_exchanged else "allreduce"), (what, d.fc_grad_path())
+
+    o.zero_grad()
+    backward(False, "no_sync")
+    backward(True, "synced after no_sync")
+    o.step()
+    o.zero_grad()
+    ex.force_capacity_once(1)  # below any count: an encoded step overflows and re-sends dense
+    backward(True, "forced capacity 1")
+    if compress and mode != "chunked":
+        assert ex.zs_stats["steps"] == 2 and ex.zs_stats["overflows"] == 1, ex.zs_stats
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("compress", [True, False])
+@pytest.mark.parametrize("mode", ["activations", "sharded", "chunked"])
+def test_exchange_step_record_dropped_after_every_backward(mode, compress):
+    launch.spawn(_w_step_record, args=(2, launch.find_free_port(), mode, compress), nprocs=2, timeout=120)
+
+
 def test_zs_codec_reference_roundtrip():
     from torch_distributed_sandbox_amd.parallel import zs
 

@@ -502,7 +502,7 @@ def forward(model, x):
         ex.begin_pooled(ya, ops.head_pooled_record(bn_b, conv2.bias, link.mag), y2.shape[1])
         link.pooled = True
     # the fc update may still be running on DDP's side stream (overlap_optimizer), or deferred to
-    # here (the activation exchange's update sweep, factored.py _Update): wait / queue it now, after
+    # here (the activation exchange's update sweep, factored.py _DeferredUpdate): wait / queue it now, after
     # the convolutions were queued, not before.  A grouped update goes to the head forward, which
     # queues it range by range
     link.fc_update = param_fence.take(fc.weight, "groups")

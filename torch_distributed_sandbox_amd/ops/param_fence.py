@@ -62,7 +62,7 @@ def take(param, kind: str):
     """The pending deferred update of ``param`` if it is its ONLY deferred item and offers the form
     ``kind`` (its ``fused_kind`` attribute), removed from the fence -- the caller runs it (the fused
     head forward runs the activation exchange's grouped update range by range,
-    parallel/factored.py ``_Update.run_until``); else None and the fence is unchanged.  Events stay
+    parallel/factored.py ``_DeferredUpdate.run_until``); else None and the fence is unchanged.  Events stay
     in the fence for the caller's :func:`wait` (under DDP's overlapped optimizer the end-of-backward
     side-stream step fences every parameter of its bucket, this one included)."""
     f = getattr(param, _ATTR, None) if param is not None else None
