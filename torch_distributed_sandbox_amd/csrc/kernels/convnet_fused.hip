@@ -219,7 +219,9 @@ __global__ __launch_bounds__(256) void l1_conv_bf3_kernel(const void* __restrict
     // the general epilogue (torch's NaN rules); otherwise no window can hold a NaN
     // (wave-uniform in an SGPR: as a per-lane bool the compiler computed both epilogues below
     // and selected, ~40 % more VALU per window)
-    const bool slow = __builtin_amdgcn_readfirstlane((__syncthreads_or(nonfinite) != 0 || !fast_ok) ? 1 : 0) != 0;
+    const int anybad = __syncthreads_or(nonfinite);
+    const bool slow = __builtin_amdgcn_readfirstlane((anybad != 0 || !fast_ok) ? 1 : 0) != 0;
+    const bool xbad = !LV && __builtin_amdgcn_readfirstlane(anybad) != 0;  // (levels are finite)
     if (t + (int)gridDim.x < total) load_tile(t + gridDim.x);
 #pragma unroll
     for (int rp = 0; rp < 2; ++rp) {
@@ -262,6 +264,35 @@ __global__ __launch_bounds__(256) void l1_conv_bf3_kernel(const void* __restrict
             else
               acc[a][c] = mfma_bf16x3(wah, wal, bh, bl, f32x4{0.f, 0.f, 0.f, 0.f});
           }
+        if constexpr (!LV) {
+          // A tile that holds a non-finite x (rare) redoes its sums on the VALU.  The MFMA sums are right
+          // for a NaN only: the split of +-inf is hi = inf, lo = inf - inf = NaN, w lo * inf and w hi * inf
+          // can differ in sign, and a zero-weight pad slot forms 0 * inf, so every output that sees an
+          // inf would be NaN where torch's conv gives +-inf (tests/test_layer1_gpu.py
+          // test_nonfinite_pixel_stays_local).  x = hi + lo (16 significant bits, hi alone when it is
+          // inf), the weights exact with the sign fold above, fp32 FMAs: inside the MFMA path's error.
+          if (xbad) {
+            float wsg[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) wsg[r] = aff[4 * g + r] < 0.f ? -1.f : 1.f;
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+              for (int c = 0; c < 2; ++c) {
+                const uint32_t* src = xs + (4 * wv + 2 * rp + a) * L1_XS + 2 + 32 * sp + 2 * li + c;
+                f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+                for (int tp = 0; tp < 25; ++tp) {
+                  const uint32_t u = src[(tp / 5) * L1_XS + tp % 5];
+                  const float hi = __uint_as_float(u & 0xFFFF0000u), lo = __uint_as_float(u << 16);
+                  const float xf = __builtin_isinf(hi) ? hi : hi + lo;
+#pragma unroll
+                  for (int r = 0; r < 4; ++r) s[r] = fmaf(wsg[r] * w1[(4 * g + r) * 25 + tp], xf, s[r]);
+                }
+                acc[a][c] = s;
+              }
+          }
+        }
         // BN1 affine -> 2x2 max-pool (first max in scan order) -> ReLU -> fp16 record +
         // argmax byte (bit 2 = ReLU passes the gradient) for channels 4g .. 4g+3
         const int prow = (r0 + 4 * wv + 2 * rp) >> 1;
@@ -1131,8 +1162,9 @@ __device__ __forceinline__ void l1_finalize_one(int e, const double* __restrict_
   const double a2 = -gm * is * is * is * sdxh / (double)n;
   const double a3 = -gm * is * sdz / (double)n - a2 * mean;
   if (j == 0) {
-    if (dgamma1) dgamma1[c] = (float)(is * sdxh);
-    if (dbeta1) dbeta1[c] = (float)sdz;
+    // (scale applies to all four gradients)
+    if (dgamma1) dgamma1[c] = (float)(scale * (is * sdxh));
+    if (dbeta1) dbeta1[c] = (float)(scale * sdz);
     // db1 = sum dy1 = a1 sdz + a2 sum y1 + a3 n  (sum y1 = n*mean)
     if (db1) db1[c] = (float)(scale * (a1 * sdz + a2 * (double)n * mean + a3 * (double)n));
   }
