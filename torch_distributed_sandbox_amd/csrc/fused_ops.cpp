@@ -24,6 +24,7 @@
 #include <mutex>
 #include <tuple>
 
+#include "kernels/l1_tiles.h"
 #include "kernels/launchers.h"
 #include "launch_check.h"
 
@@ -848,6 +849,22 @@ Tensor conv2_bwd_walk_table(int64_t B, int64_t tiles_r, int64_t tiles_c, int64_t
   return t;
 }
 
+// The layer-1 kernels' tile walk (kernels/l1_tiles.h) of the workgroup whose first list entry is t0,
+// run on the host: the first n tiles as rows (b, tile row, tile col) of a CPU int tensor; rows past
+// the list have b >= B.  For tests.
+Tensor l1_tile_walk(int64_t t0, int64_t grid, int64_t tiles_r, int64_t tiles_c, int64_t n) {
+  TORCH_CHECK(t0 >= 0 && grid >= 1 && tiles_r >= 1 && tiles_c >= 1 && n >= 0, "l1_tile_walk: bad arguments");
+  auto t = at::empty({n, 3}, at::TensorOptions().dtype(at::kInt));
+  int* o = t.data_ptr<int>();
+  tds::L1Walk w = tds::l1_walk_begin((int)t0, (int)grid, (int)tiles_r, (int)tiles_c);
+  for (int64_t i = 0; i < n; ++i, tds::l1_walk_next(w, (int)tiles_r, (int)tiles_c)) {
+    o[3 * i] = w.b;
+    o[3 * i + 1] = w.tr;
+    o[3 * i + 2] = w.tc;
+  }
+  return t;
+}
+
 // Per-wave barrier-wait clocks of the last conv2 backward launch of a TDS_CONV2_DIAG=13 diag
 // build ([nwg][8][wait, total] shader-clock cycles; zeros in production builds).
 Tensor conv2_bwd_clock_dump(int64_t nwg) {
@@ -1345,6 +1362,7 @@ TORCH_LIBRARY_FRAGMENT(tdsa, m) {
   m.def("mag_ypart_count() -> int", &mag_ypart_count);
   m.def("conv2_bwd_clock_dump(int nwg) -> Tensor", &conv2_bwd_clock_dump);
   m.def("conv2_bwd_walk_table(int B, int tiles_r, int tiles_c, int nwg, int seg) -> Tensor", &conv2_bwd_walk_table);
+  m.def("l1_tile_walk(int t0, int grid, int tiles_r, int tiles_c, int n) -> Tensor", &l1_tile_walk);
   m.def(
       "fused_conv2_backward_y2(Tensor y2, Tensor a2, Tensor g2m, Tensor aff2, Tensor kbuf, Tensor b2, Tensor(c!) mag, Tensor p1, "
       "Tensor wd, "

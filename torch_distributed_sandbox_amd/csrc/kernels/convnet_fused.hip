@@ -23,6 +23,7 @@
 #include "launchers.h"
 #include "xmom_u8.h"
 #include "conv2_pack.h"
+#include "l1_tiles.h"
 
 namespace tds {
 
@@ -91,13 +92,17 @@ __global__ __launch_bounds__(256) void l1_conv_bf3_kernel(const void* __restrict
                                                       const float* __restrict__ b1, const float* __restrict__ aff,
                                                       uint4* __restrict__ p1, uint8_t* __restrict__ idx1, int B,
                                                       int H, int W) {
-  __shared__ __attribute__((aligned(16))) uint32_t xs[L1_XR * L1_XS];  // x as (bf16 hi << 16 | bf16 lo)
+  // x as (bf16 hi << 16 | bf16 lo), two buffers: tile k stages into buffer k & 1 while slower waves
+  // still read tile k - 1 from the other one, so ONE barrier per tile (staged -> read) is enough:
+  // a wave that stages tile k + 1 has passed barrier k, which every wave reaches only after its
+  // reads of tile k - 1, the buffer's previous user
+  constexpr int XSW = L1_XR * L1_XS;
+  __shared__ __attribute__((aligned(16))) uint32_t xs[2 * XSW];
   constexpr bool PAIR = LV;  // level input: pair words (l1_pair)
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int li = lane & 15, g = lane >> 4;
   const int P = H / 2, PW = W / 2;
   const int tiles_c = (W + L1_TC - 1) / L1_TC, tiles_r = (H + L1_TR - 1) / L1_TR;
-  const int per_img = tiles_c * tiles_r, total = per_img * B;
 
   // A operand (weights) in registers as bf16 hi / lo: lane -> co = li, k = 8g + j -> tap
   // l1b_tap(g, j) (rows ky = g plus row 4 spread over g = 0, 1; pads carry weight 0)
@@ -144,44 +149,100 @@ __global__ __launch_bounds__(256) void l1_conv_bf3_kernel(const void* __restrict
 #pragma unroll
     for (int r = 0; r < 4; ++r) ea[r] *= L1_LEVEL_SCALE;  // z = ea * (scale * acc + b1) + eb
   }
-  const float* __restrict__ x = static_cast<const float*>(xv);
-  const uint8_t* __restrict__ xl = static_cast<const uint8_t*>(xv);
 
   // x tile staging: LDS column 0 <-> global column c0-4 (16-B aligned since W % 4 == 0),
   // 20 rows x 18 float4; the next tile's loads are issued before this tile's MFMAs.
   constexpr int NV = L1_XR * 18;
   constexpr int PER = (NV + 255) / 256;
   float4 pre[PER];  // LV: .x = 4 levels, .y = the next 4 (the pair words' right neighbours)
-  // unconditional loads (out-of-range lanes read a zero vector): a load under a per-lane branch
-  // is waited for before the branches merge (conv2_bwd.hip, l1_bwd_mfma_kernel)
-  auto load_tile = [&](int t) {
-    const int b = t / per_img, rem = t - b * per_img;
-    const int r0 = (rem / tiles_c) * L1_TR, c0 = (rem % tiles_c) * L1_TC;
+  // A thread's share of the staging addresses, once: vector e = tid + 256 u is row rr, float4
+  // column cv of the 20 x 72 window -> its byte offset from the window's first element and its LDS
+  // word.  Vectors past the window (u = 1, tid >= 104) take vector tid's offset: on an interior
+  // tile they load a word of the window again (never staged) instead of selecting the zero source.
+  constexpr uint32_t ESZ = LV ? 1 : 4;
+  uint32_t ld_off[PER], xs_off[PER];
 #pragma unroll
-    for (int u = 0; u < PER; ++u) {
-      const int e = tid + 256 * u;
-      const int rr = e / 18, cv = e - rr * 18;
-      const int gr = r0 - 2 + rr, gc = c0 - 4 + 4 * cv;
-      const bool ok = (e < NV) & ((uint32_t)gr < (uint32_t)H) & ((uint32_t)gc < (uint32_t)W);
-      const int64_t o = ((int64_t)b * H + gr) * W + gc;
-      if constexpr (LV) {  // 4 levels in .x, the next 4 in .y (zero past the image / the tile)
+  for (int u = 0; u < PER; ++u) {
+    const int e = tid + 256 * u, ev = e < NV ? e : tid;
+    const int rr = ev / 18, cv = ev - rr * 18;
+    ld_off[u] = (uint32_t)(rr * W + 4 * cv) * ESZ;
+    xs_off[u] = (uint32_t)(rr * L1_XS + 4 * cv);
+  }
+  // unconditional loads (out-of-range lanes read a zero vector): a load under a per-lane branch
+  // is waited for before the branches merge (conv2_bwd.hip, l1_bwd_mfma_kernel).  The tile forms
+  // one scalar 64-bit base (image rows fit 32 bits); a tile whose window lies inside the image
+  // adds base and offset behind a scalar branch, a border tile keeps the per-lane bounds.  The
+  // branch picks addresses only: the loads themselves follow it, on every path.
+  auto load_tile = [&](int b, int tr, int tc) {
+    const int r0 = tr * L1_TR, c0 = tc * L1_TC;
+    const char* base = static_cast<const char*>(xv) + ((int64_t)(b * H + r0 - 2) * W + (c0 - 4)) * (int64_t)ESZ;
+    const char* src[PER];
+    const char* srn[PER];
+    // (levels: the pair words' right neighbours reach 4 columns further; word 71's, never read by
+    // an MFMA, is then the next 4 levels and not zero)
+    if (r0 >= 2 && c0 >= 4 && r0 + L1_TR + 2 <= H && c0 + L1_TC + (LV ? 8 : 4) <= W) {
+#pragma unroll
+      for (int u = 0; u < PER; ++u) {
+        src[u] = base + ld_off[u];
+        srn[u] = src[u] + 4;
+      }
+    } else {
+      // (the thread index laundered: the per-lane row / column arithmetic of this rare path is not
+      // hoisted out of the tile loop into registers the steady path then carries)
+      int tb = tid;
+      asm volatile("" : "+v"(tb));
+#pragma unroll
+      for (int u = 0; u < PER; ++u) {
+        const int e = tb + 256 * u;
+        const int rr = e / 18, cv = e - rr * 18;
+        const int gr = r0 - 2 + rr, gc = c0 - 4 + 4 * cv;
+        const bool ok = (e < NV) & ((uint32_t)gr < (uint32_t)H) & ((uint32_t)gc < (uint32_t)W);
         // (its own range test: at the image's left edge the word at column -1 pairs with x[0])
         const bool okn = (e < NV) & (cv < 17) & ((uint32_t)gr < (uint32_t)H) & ((uint32_t)(gc + 4) < (uint32_t)W);
-        const uint32_t* src = ok ? reinterpret_cast<const uint32_t*>(xl + o) : &g_l1b_zero.x;
-        const uint32_t* srn = okn ? reinterpret_cast<const uint32_t*>(xl + o + 4) : &g_l1b_zero.x;
-        pre[u] = make_float4(__uint_as_float(*src), PAIR ? __uint_as_float(*srn) : 0.f, 0.f, 0.f);
-      } else {
-        const float4* src = ok ? reinterpret_cast<const float4*>(x + o) : reinterpret_cast<const float4*>(&g_l1b_zero);
-        pre[u] = *src;
+        src[u] = ok ? base + ld_off[u] : reinterpret_cast<const char*>(&g_l1b_zero);
+        srn[u] = okn ? base + ld_off[u] + 4 : reinterpret_cast<const char*>(&g_l1b_zero);
       }
     }
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      if constexpr (LV)  // 4 levels in .x, the next 4 in .y (zero past the image / the tile)
+        pre[u] = make_float4(__uint_as_float(*reinterpret_cast<const uint32_t*>(src[u])),
+                             __uint_as_float(*reinterpret_cast<const uint32_t*>(srn[u])), 0.f, 0.f);
+      else
+        pre[u] = *reinterpret_cast<const float4*>(src[u]);
+    }
   };
-  int t = xcd_remap(blockIdx.x, gridDim.x);
-  if (t < total) load_tile(t);
-  for (; t < total; t += gridDim.x) {
-    const int b = t / per_img, rem = t - b * per_img;
-    const int r0 = (rem / tiles_c) * L1_TR, c0 = (rem % tiles_c) * L1_TC;
-    __syncthreads();
+  // LDS read bases of the pair-word layout (bytes): a lane's pairs p = 0, 1, 2 are 2 words apart
+  // (l1_pair: one row), p = 3 is irregular, so an operand (row a, column c) reads from two per-lane
+  // bases and everything else -- p, rp, sp -- is the instruction's offset field.  Each (a, c) has
+  // bases of its own, opaque to the compiler: reads of one base that it merges into ds_read2_b32
+  // then feed ONE operand's consecutive registers (p = 0, 1); merged across operands, each result
+  // pair straddled two MFMA operands and cost 3 v_mov per operand.
+  uint32_t la[2][2], lb[2][2];
+  if constexpr (PAIR) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const int i0 = (4 * wv + a) * L1_XS + 2 + 2 * li + c;  // +2: tile origin is c0-4
+        la[a][c] = 4u * (uint32_t)(i0 + koff[0]);
+        lb[a][c] = 4u * (uint32_t)(i0 + koff[3]);
+        asm volatile("" : "+v"(la[a][c]), "+v"(lb[a][c]));
+      }
+  }
+  // A thread's share of its p1 record's address (bytes; idx1's 16-B records: half of it): pooled row
+  // 2 wv, column li of the tile, channels 4g..; (rp, sp) and the tile add scalars
+  const uint32_t po = (uint32_t)((2 * wv * PW + li) * 32 + g * 8);
+  const int wvs = __builtin_amdgcn_readfirstlane(wv);
+  L1Walk wk = l1_walk_begin(xcd_remap(blockIdx.x, gridDim.x), (int)gridDim.x, tiles_r, tiles_c);
+  if (wk.b < B) load_tile(wk.b, wk.tr, wk.tc);
+  int buf = 0;  // word offset of this tile's xs buffer
+  for (; wk.b < B; buf = XSW - buf) {
+    // this tile's first pooled record and the pooled rows / columns the image has from there
+    const int pr0 = wk.tr * (L1_TR / 2), pc0 = wk.tc * (L1_TC / 2);
+    const int64_t recb = (int64_t)(wk.b * P + pr0) * PW + pc0;
+    const int ph = P - pr0, pw = PW - pc0;
+    l1_walk_next(wk, tiles_r, tiles_c);
     bool nonfinite = false;
 #pragma unroll
     for (int u = 0; u < PER; ++u) asm volatile("" ::"v"(pre[u].x), "v"(pre[u].y), "v"(pre[u].z), "v"(pre[u].w));
@@ -189,7 +250,7 @@ __global__ __launch_bounds__(256) void l1_conv_bf3_kernel(const void* __restrict
     for (int u = 0; u < PER; ++u) {
       const int e = tid + 256 * u;
       if (e < NV) {
-        const int rr = e / 18, cv = e - rr * 18;
+        uint32_t* dst = xs + buf + xs_off[u];
         if constexpr (PAIR) {  // levels are exact in bf16 (the fp32 bits' upper half): pair words
           const uint32_t q = __float_as_uint(pre[u].x);
           const uint32_t f0 = __float_as_uint((float)(q & 0xFFu)), f1 = __float_as_uint((float)((q >> 8) & 0xFFu));
@@ -200,7 +261,7 @@ __global__ __launch_bounds__(256) void l1_conv_bf3_kernel(const void* __restrict
           v.y = __builtin_amdgcn_perm(f2, f1, 0x07060302u);
           v.z = __builtin_amdgcn_perm(f3, f2, 0x07060302u);
           v.w = __builtin_amdgcn_perm(f4, f3, 0x07060302u);
-          l1_store4(xs + rr * L1_XS + 4 * cv, v);
+          l1_store4(dst, v);
           continue;
         }
         nonfinite |= !__builtin_isfinite((pre[u].x + pre[u].y) + (pre[u].z + pre[u].w));
@@ -212,17 +273,31 @@ __global__ __launch_bounds__(256) void l1_conv_bf3_kernel(const void* __restrict
         v.y = __builtin_amdgcn_perm(h01, l01, 0x07060302u);
         v.z = __builtin_amdgcn_perm(h23, l23, 0x05040100u);
         v.w = __builtin_amdgcn_perm(h23, l23, 0x07060302u);
-        l1_store4(xs + rr * L1_XS + 4 * cv, v);
+        l1_store4(dst, v);
       }
     }
     // a non-finite x anywhere in the tile (or a degenerate BN1 affine) sends the whole tile to
     // the general epilogue (torch's NaN rules); otherwise no window can hold a NaN
     // (wave-uniform in an SGPR: as a per-lane bool the compiler computed both epilogues below
     // and selected, ~40 % more VALU per window)
-    const int anybad = __syncthreads_or(nonfinite);
+    // Levels are finite: no vote, the tile's one barrier is a plain one and slow is fixed for the
+    // launch.  (The vote cost a wave-OR, an LDS round trip and three more barriers per tile.)
+    int anybad = 0;
+    if constexpr (LV) __syncthreads();
+    else anybad = __syncthreads_or(nonfinite);
     const bool slow = __builtin_amdgcn_readfirstlane((anybad != 0 || !fast_ok) ? 1 : 0) != 0;
-    const bool xbad = !LV && __builtin_amdgcn_readfirstlane(anybad) != 0;  // (levels are finite)
-    if (t + (int)gridDim.x < total) load_tile(t + gridDim.x);
+    const bool xbad = !LV && __builtin_amdgcn_readfirstlane(anybad) != 0;
+    if (wk.b < B) load_tile(wk.b, wk.tr, wk.tc);
+    uint32_t qa[2][2], qb[2][2];  // the bases in this tile's buffer
+    if constexpr (PAIR) {
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          qa[a][c] = la[a][c] + 4u * (uint32_t)buf;
+          qb[a][c] = lb[a][c] + 4u * (uint32_t)buf;
+        }
+    }
 #pragma unroll
     for (int rp = 0; rp < 2; ++rp) {
 #pragma unroll
@@ -236,19 +311,19 @@ __global__ __launch_bounds__(256) void l1_conv_bf3_kernel(const void* __restrict
 #pragma unroll
           for (int c = 0; c < 2; ++c) {
             const int row = 4 * wv + 2 * rp + a;
-            const uint32_t* src = xs + row * L1_XS + 2 + 32 * sp + 2 * li + c;  // +2: tile origin is c0-4
+            const uint32_t* src = xs + buf + row * L1_XS + 2 + 32 * sp + 2 * li + c;  // +2: tile origin is c0-4
             s16x8 bh, bl;
             uint32_t* hp = reinterpret_cast<uint32_t*>(&bh);
             uint32_t* lp = reinterpret_cast<uint32_t*>(&bl);
             if constexpr (PAIR) {  // pair words: the B operand as read (l1_pair)
-              // (the c = 1 base laundered: merged with c = 0's reads into ds_read2_b32, each
-              // result pair straddled two MFMA operands and cost 3 v_mov per operand)
-              // (the word index, not the pointer: a laundered pointer loses the LDS address space
-              // and becomes flat loads, whose vmcnt wait also drains the x prefetch)
-              int i0 = row * L1_XS + 2 + 32 * sp + 2 * li + c;
-              if (c == 1) asm volatile("" : "+v"(i0));
+              // (offsets from xs, not laundered pointers: those lose the LDS address space and
+              // become flat loads, whose vmcnt wait also drains the x prefetch)
+              const uint32_t o = (uint32_t)(2 * rp * L1_XS + 32 * sp) * 4u;
+              const char* xb = reinterpret_cast<const char*>(xs);
+              auto rd = [&](uint32_t at) { return *reinterpret_cast<const uint32_t*>(xb + at); };
               typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-              bh = __builtin_bit_cast(s16x8, u32x4{xs[i0 + koff[0]], xs[i0 + koff[1]], xs[i0 + koff[2]], xs[i0 + koff[3]]});
+              bh = __builtin_bit_cast(s16x8, u32x4{rd(qa[a][c] + o), rd(qa[a][c] + o + 8), rd(qa[a][c] + o + 16),
+                                                   rd(qb[a][c] + o)});
             } else {
               uint32_t u[8];
 #pragma unroll
@@ -279,7 +354,7 @@ __global__ __launch_bounds__(256) void l1_conv_bf3_kernel(const void* __restrict
             for (int a = 0; a < 2; ++a)
 #pragma unroll
               for (int c = 0; c < 2; ++c) {
-                const uint32_t* src = xs + (4 * wv + 2 * rp + a) * L1_XS + 2 + 32 * sp + 2 * li + c;
+                const uint32_t* src = xs + buf + (4 * wv + 2 * rp + a) * L1_XS + 2 + 32 * sp + 2 * li + c;
                 f32x4 s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
                 for (int tp = 0; tp < 25; ++tp) {
@@ -295,12 +370,10 @@ __global__ __launch_bounds__(256) void l1_conv_bf3_kernel(const void* __restrict
         }
         // BN1 affine -> 2x2 max-pool (first max in scan order) -> ReLU -> fp16 record +
         // argmax byte (bit 2 = ReLU passes the gradient) for channels 4g .. 4g+3
-        const int prow = (r0 + 4 * wv + 2 * rp) >> 1;
-        const int pcol = (c0 >> 1) + 16 * sp + li;
         float pv[4];
         uint32_t ixw = 0;
         // scan order: (row 0, col 0), (row 0, col 1), (row 1, col 0), (row 1, col 1)
-        if (!slow) {  // every z finite (tile-uniform)
+        if (__builtin_expect(!slow, 1)) {  // every z finite (tile-uniform)
           float mz[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
@@ -343,13 +416,13 @@ __global__ __launch_bounds__(256) void l1_conv_bf3_kernel(const void* __restrict
         }
         // p1 is conv2's single fp16 operand (bf16x3.h, fp16x2): one rounding, 32-B records
         const uint32_t h01 = cvt2_f16(pv[0], pv[1]), h23 = cvt2_f16(pv[2], pv[3]);
-        if (prow < P && pcol < PW) {
-          const int64_t rec = ((int64_t)b * P + prow) * PW + pcol;
-          uint2* dst = reinterpret_cast<uint2*>(p1 + rec * 2);  // 32-B record: fp16[16]
-          // (non-temporal: plain, allocating p1 stores cost the layer-1 conv +14 us and the conv2
-          // forward +23 us, r5_s44)
-          st_stream(dst + g, make_uint2(h01, h23));
-          if constexpr (IDX) st_stream(reinterpret_cast<uint32_t*>(idx1 + rec * 16) + g, ixw);
+        // the record of (tile, rp, sp, pooled row 2 wv, column 0) is a scalar; the row test is one too
+        const int64_t rec = recb + (rp * PW + 16 * sp);
+        if ((2 * wvs + rp < ph) & (16 * sp + li < pw)) {
+          // 32-B records: fp16[16] (non-temporal: plain, allocating p1 stores cost the layer-1 conv
+          // +14 us and the conv2 forward +23 us, r5_s44)
+          st_stream(reinterpret_cast<uint2*>(reinterpret_cast<char*>(p1) + rec * 32 + po), make_uint2(h01, h23));
+          if constexpr (IDX) st_stream(reinterpret_cast<uint32_t*>(idx1 + rec * 16 + (po >> 1)), ixw);
         }
       }
     }
@@ -530,7 +603,10 @@ constexpr int LM_X_BYTES = LB_XR * LM_XS * 4;
 // the end.
 // waves per SIMD the register budget is cut for (4: <= 128 VGPRs, 4 workgroups per CU with
 // fused_ops.cpp l1b_wg(); 3: <= 168, the measured configuration -- the compiler then keeps the
-// default variants at 124-126 VGPRs, so 4 workgroups still fit a CU)
+// default variants at 124-126 VGPRs, so 4 workgroups still fit a CU).  The level variant is cut
+// for 5 (<= 96 VGPRs, which it sits at with its reads one K-step ahead: the 5 workgroups per CU
+// l1b_wg() launches stay resident; under the budget of 3 the per-thread address parts alone took
+// it from 87 to 97, one allocation granule too many)
 constexpr int L1B_WAVES = 3;
 // Level input: dz1 * x on ONE v_mfma_f32_16x16x32_f16 per product instead of
 // the bf16 pair (dz hi, dz lo): dz1 is dp1h's fp16 value as stored and a level (0..255) is exact
@@ -541,7 +617,7 @@ constexpr int L1B_WAVES = 3;
 // the pair (1.0, 1.0).  (A conflict-free bf16-pair x tile, two MFMAs per product, timed slower and
 // is in git history.)  fp32 images (!LV): bf16x3, the x operand split hi + lo.
 template <bool LV>
-__global__ __launch_bounds__(256, L1B_WAVES) void l1_bwd_mfma_kernel(const void* __restrict__ xv, const uint4* __restrict__ dp1,
+__global__ __launch_bounds__(256, LV ? 5 : L1B_WAVES) void l1_bwd_mfma_kernel(const void* __restrict__ xv, const uint4* __restrict__ dp1,
                                                           const uint32_t* __restrict__ dp1_dec,
                                                           const uint4* __restrict__ p1, const uint8_t* __restrict__ idx1,
                                                           double* __restrict__ partial, int B, int H, int W) {
@@ -554,7 +630,6 @@ __global__ __launch_bounds__(256, L1B_WAVES) void l1_bwd_mfma_kernel(const void*
   const int li = lane & 15, g = lane >> 4;
   const int P = H / 2, PW = W / 2, PG = (PW + 3) >> 2;
   const int tiles_c = (PW + LB_PC - 1) / LB_PC, tiles_r = (P + LB_PR - 1) / LB_PR;
-  const int per_img = tiles_c * tiles_r, total = per_img * B;
   const double dec = (double)__uint_as_float(dp1_dec[0]);
 
   // K ordering of a K-step (2 rows x 16 columns = 8 pooling windows): k = 4*w + 2*dr + dc, so
@@ -573,51 +648,84 @@ __global__ __launch_bounds__(256, L1B_WAVES) void l1_bwd_mfma_kernel(const void*
   // the ones block (never overwritten: the x tile uses columns 0..71)
   for (int e = tid; e < LB_XR * (LM_XS - 72); e += 256)  // bf16 1.0 | lo 0, or fp16 1.0 << 16
     xs[(e / (LM_XS - 72)) * LM_XS + 72 + e % (LM_XS - 72)] = H16 ? 0x3C003C00u : 0x3F800000u;
-  const float* __restrict__ x = static_cast<const float*>(xv);
-  const uint8_t* __restrict__ xl = static_cast<const uint8_t*>(xv);
   uint4 pre[LB_PER];
   // One unconditional load per vector u: the class of vector u (dp1 records, argmax bytes, x
   // words) is a compile-time property of u (LB_V_DP and LB_V_ID are multiples of 256, the block is
   // 256 threads), and lanes out of range read a zero vector.  (Loads under per-lane branches had
   // to land before the branches merged: the compiler waited for each one right after issuing it,
   // which serialised the whole prefetch.)
-  auto load_tile = [&](int t) {
-    // tiles last-to-first, the reverse of the conv2 backward's dp1 writes: the first tiles read are
-    // the most recent writes, still in the Infinity Cache (129.8 -> 128.0 us r5_s44, 132.8 -> 129.8
-    // r5_s50)
-    t = total - 1 - t;
-    const int b = t / per_img, rem = t - b * per_img;
-    const int pr0 = (rem / tiles_c) * LB_PR, pc0 = (rem % tiles_c) * LB_PC;
+  // A thread's share of every load address (bytes from the tile's first dp1h record, idx1 record
+  // and x window element) and of the x words' LDS offsets, once.  x vectors past the window (the
+  // last u, tid >= 104) take vector tid's offset, as in l1_conv_bf3_kernel.
+  constexpr uint32_t ESZ = LV ? 1 : 4;
+  constexpr int U_X = (LB_V_DP + LB_V_ID) / 256;  // the first x vector's u
+  uint32_t ld_off[LB_PER], xs_off[LB_PER - U_X];
 #pragma unroll
-    for (int u = 0; u < LB_PER; ++u) {
-      const int e = tid + 256 * u;
-      if (256 * u < LB_V_DP) {  // dp1h: 64 vectors per tile row (8 column groups x 8)
-        const int gpr = pr0 + (e >> 6), cg = (pc0 >> 2) + ((e >> 3) & 7);
-        const int64_t rec = ((int64_t)b * P + gpr) * PG + cg;
-        const uint4* src = ((gpr < P) & (cg < PG)) ? dp1 + rec * 8 + (e & 7) : &g_l1b_zero;
-        pre[u] = *src;
-      } else if (256 * u < LB_V_DP + LB_V_ID) {
-        const int pp = e - LB_V_DP;
-        const int gpr = pr0 + pp / LB_PC, gpc = pc0 + pp % LB_PC;
-        const int64_t rec = ((int64_t)b * P + gpr) * PW + gpc;
-        const uint4* src = ((gpr < P) & (gpc < PW)) ? reinterpret_cast<const uint4*>(idx1) + rec : &g_l1b_zero;
-        pre[u] = *src;
-      } else {
-        const int ex = e - LB_V_DP - LB_V_ID;
-        const int rr = ex / 18, cv = ex - rr * 18;
-        const int gr = 2 * pr0 - 2 + rr, gcol = 2 * pc0 - 4 + 4 * cv;
-        const bool ok = (ex < LB_V_X) & ((uint32_t)gr < (uint32_t)H) & ((uint32_t)gcol < (uint32_t)W);
-        const int64_t o = ((int64_t)b * H + gr) * W + gcol;
-        if constexpr (LV) {  // 4 levels in .x; H16: the next 4 in .y (the pair words' right neighbours)
-          const uint32_t* src = ok ? reinterpret_cast<const uint32_t*>(xl + o) : &g_l1b_zero.x;
-          const bool okn = (ex < LB_V_X) & (cv < 17) & ((uint32_t)gr < (uint32_t)H) & ((uint32_t)(gcol + 4) < (uint32_t)W);
-          const uint32_t* srn = okn ? reinterpret_cast<const uint32_t*>(xl + o + 4) : &g_l1b_zero.x;
-          pre[u] = make_uint4(*src, H16 ? *srn : 0u, 0u, 0u);
+  for (int u = 0; u < LB_PER; ++u) {
+    const int e = tid + 256 * u;
+    if (256 * u < LB_V_DP) {  // dp1h: 64 vectors per tile row (8 column groups x 8); vector tid's offset
+      // for every u: u adds 4 tile rows, a scalar (one register for the class)
+      ld_off[u] = (uint32_t)(((tid >> 6) * PG + ((tid >> 3) & 7)) * 8 + (tid & 7)) * 16u;
+    } else if (256 * u < LB_V_DP + LB_V_ID) {
+      const int pp = e - LB_V_DP;
+      ld_off[u] = (uint32_t)((pp / LB_PC) * PW + pp % LB_PC) * 16u;
+    } else {
+      const int ex = e - LB_V_DP - LB_V_ID, ev = ex < LB_V_X ? ex : tid;
+      const int rr = ev / 18, cv = ev - rr * 18;
+      ld_off[u] = (uint32_t)(rr * W + 4 * cv) * ESZ;
+      xs_off[u - U_X] = (uint32_t)(rr * LM_XS + 4 * cv);
+    }
+  }
+  // The tile forms three scalar 64-bit bases; a tile that lies inside the image with its x window
+  // adds base and offset behind a scalar branch, a border tile keeps the per-lane bounds and the
+  // zero source.  The branch picks addresses only: the loads follow it, on every path.
+  auto load_tile = [&](int b, int tr, int tc) {
+    const int pr0 = tr * LB_PR, pc0 = tc * LB_PC;
+    const char* dbase = reinterpret_cast<const char*>(dp1) + ((int64_t)(b * P + pr0) * PG + (pc0 >> 2)) * 128;
+    const char* ibase = reinterpret_cast<const char*>(idx1) + ((int64_t)(b * P + pr0) * PW + pc0) * 16;
+    const char* xbase = static_cast<const char*>(xv) + ((int64_t)(b * H + 2 * pr0 - 2) * W + (2 * pc0 - 4)) * (int64_t)ESZ;
+    auto drow = [&](int u) { return dbase + (int64_t)(4 * u * PG) * 128; };
+    const char* src[LB_PER];
+    const char* srn[LB_PER - U_X];
+    // (levels: the pair words' right neighbours reach 4 columns further, see l1_conv_bf3_kernel)
+    if (pr0 >= 1 && pc0 >= 2 && pr0 + LB_PR + 1 <= P && 2 * (pc0 + LB_PC) + (LV ? 8 : 4) <= W) {
+#pragma unroll
+      for (int u = 0; u < LB_PER; ++u) {
+        src[u] = (256 * u < LB_V_DP ? drow(u) : 256 * u < LB_V_DP + LB_V_ID ? ibase : xbase) + ld_off[u];
+        if (u >= U_X) srn[u - U_X] = src[u] + 4;
+      }
+    } else {
+      const char* zero = reinterpret_cast<const char*>(&g_l1b_zero);
+      int tb = tid;  // (laundered: see l1_conv_bf3_kernel)
+      asm volatile("" : "+v"(tb));
+#pragma unroll
+      for (int u = 0; u < LB_PER; ++u) {
+        const int e = tb + 256 * u;
+        if (256 * u < LB_V_DP) {
+          const int gpr = pr0 + (e >> 6), cg = (pc0 >> 2) + ((e >> 3) & 7);
+          src[u] = ((gpr < P) & (cg < PG)) ? drow(u) + ld_off[u] : zero;
+        } else if (256 * u < LB_V_DP + LB_V_ID) {
+          const int pp = e - LB_V_DP;
+          const int gpr = pr0 + pp / LB_PC, gpc = pc0 + pp % LB_PC;
+          src[u] = ((gpr < P) & (gpc < PW)) ? ibase + ld_off[u] : zero;
         } else {
-          const uint4* src = ok ? reinterpret_cast<const uint4*>(x + o) : &g_l1b_zero;
-          pre[u] = *src;
+          const int ex = e - LB_V_DP - LB_V_ID;
+          const int rr = ex / 18, cv = ex - rr * 18;
+          const int gr = 2 * pr0 - 2 + rr, gcol = 2 * pc0 - 4 + 4 * cv;
+          const bool ok = (ex < LB_V_X) & ((uint32_t)gr < (uint32_t)H) & ((uint32_t)gcol < (uint32_t)W);
+          const bool okn = (ex < LB_V_X) & (cv < 17) & ((uint32_t)gr < (uint32_t)H) & ((uint32_t)(gcol + 4) < (uint32_t)W);
+          src[u] = ok ? xbase + ld_off[u] : zero;
+          srn[u - U_X] = okn ? xbase + ld_off[u] + 4 : zero;
         }
       }
+    }
+#pragma unroll
+    for (int u = 0; u < LB_PER; ++u) {
+      if (LV && u >= U_X)  // 4 levels in .x; H16: the next 4 in .y (the pair words' right neighbours)
+        pre[u] = make_uint4(*reinterpret_cast<const uint32_t*>(src[u]),
+                            H16 ? *reinterpret_cast<const uint32_t*>(srn[u - U_X]) : 0u, 0u, 0u);
+      else
+        pre[u] = *reinterpret_cast<const uint4*>(src[u]);
     }
   };
   auto store_tile = [&]() {
@@ -633,14 +741,13 @@ __global__ __launch_bounds__(256, L1B_WAVES) void l1_bwd_mfma_kernel(const void*
       else if (e < LB_V_DP + LB_V_PH) reinterpret_cast<uint4*>(phs)[e - LB_V_DP] = pre[u];
       else if (e < LB_V_DP + LB_V_PH + LB_V_ID) reinterpret_cast<uint4*>(ids)[e - LB_V_DP - LB_V_PH] = pre[u];
       else if (e < LB_V) {
-        e -= LB_V_DP + LB_V_PH + LB_V_ID;
-        const int rr = e / 18, cv = e - rr * 18;
+        uint32_t* dst = xs + xs_off[u >= U_X ? u - U_X : 0];
         if constexpr (H16) {  // pair words: fp16 x[c] | fp16 x[c+1] << 16 (levels are exact)
           const uint32_t q = pre[u].x;
           auto h = [](uint32_t l) { return (uint32_t)__builtin_bit_cast(unsigned short, (_Float16)(float)l); };
           const uint32_t h0 = h(q & 0xFFu), h1 = h((q >> 8) & 0xFFu), h2 = h((q >> 16) & 0xFFu), h3 = h(q >> 24);
           const uint32_t h4 = h(pre[u].y & 0xFFu);
-          lb_store4(xs + rr * LM_XS + 4 * cv, make_uint4(h0 | h1 << 16, h1 | h2 << 16, h2 | h3 << 16, h3 | h4 << 16));
+          lb_store4(dst, make_uint4(h0 | h1 << 16, h1 | h2 << 16, h2 | h3 << 16, h3 | h4 << 16));
           continue;
         }
         const float4 f = __builtin_bit_cast(float4, pre[u]);
@@ -652,7 +759,7 @@ __global__ __launch_bounds__(256, L1B_WAVES) void l1_bwd_mfma_kernel(const void*
         v.y = __builtin_amdgcn_perm(h01, l01, 0x07060302u);
         v.z = __builtin_amdgcn_perm(h23, l23, 0x05040100u);
         v.w = __builtin_amdgcn_perm(h23, l23, 0x07060302u);
-        lb_store4(xs + rr * LM_XS + 4 * cv, v);  // odd row stride: dword stores
+        lb_store4(dst, v);  // odd row stride: dword stores
       }
     }
   };
@@ -663,14 +770,73 @@ __global__ __launch_bounds__(256, L1B_WAVES) void l1_bwd_mfma_kernel(const void*
 #pragma unroll
     for (int r = 0; r < 4; ++r) dacc[blk][r] = 0.0;
 
-  int t = xcd_remap(blockIdx.x, gridDim.x);
-  if (t < total) load_tile(t);
-  for (; t < total; t += gridDim.x) {
+  // tiles last-to-first, the reverse of the conv2 backward's dp1 writes: the first tiles read are
+  // the most recent writes, still in the Infinity Cache (129.8 -> 128.0 us r5_s44, 132.8 -> 129.8
+  // r5_s50).  List entry t is tile total - 1 - t: each coordinate of the walk counted from its end.
+  L1Walk wk = l1_walk_begin(xcd_remap(blockIdx.x, gridDim.x), (int)gridDim.x, tiles_r, tiles_c);
+  auto load_walk = [&]() { load_tile(B - 1 - wk.b, tiles_r - 1 - wk.tr, tiles_c - 1 - wk.tc); };
+  if (wk.b < B) load_walk();
+  while (wk.b < B) {
+    l1_walk_next(wk, tiles_r, tiles_c);
     __syncthreads();
     store_tile();
     __syncthreads();
-    if (t + (int)gridDim.x < total) load_tile(t + gridDim.x);
+    if (wk.b < B) load_walk();
     f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+    if constexpr (H16) {
+      // Level input: the 8 K-steps (h, sg) of the tile with their LDS reads one step ahead.  A step's
+      // dp1h pair word, two argmax bytes and two B operands are read while the step before it routes
+      // its dz1 and issues its MFMAs (scheduling fences keep that order), so only the tile's first
+      // step waits for a read it has just issued.
+      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+      struct KOps {
+        uint32_t dpair, ab[2];
+        u32x4 b[2];
+      };
+      auto rd = [&](int k) {
+        const int rp = 2 * wv + (k >> 2), sg = k & 3;
+        KOps o;
+        // pooled columns 8sg + 2g + {0, 1}: column group 2sg + (g >> 1), pixels 2(g & 1) + {0, 1} --
+        // one dword (a 32-lane half reads 32 consecutive words: conflict-free)
+        o.dpair = dps[((rp * 8 + 2 * sg + (g >> 1)) * 16 + li) * 2 + (g & 1)];
+#pragma unroll
+        for (int wi = 0; wi < 2; ++wi) o.ab[wi] = ids[(rp * LB_PC + 8 * sg + 2 * g + wi) * 16 + li];
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk) {  // dword 2 dr + wi = (window wi, row dr), cols dc = 0, 1: one pair word
+          const int bo = 2 * rp * LM_XS + 16 * sg + boff[blk];
+          o.b[blk] = u32x4{xs[bo], xs[bo + 2], xs[bo + LM_XS], xs[bo + LM_XS + 2]};
+        }
+        return o;
+      };
+      KOps cur = rd(0);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        KOps nxt = cur;
+        if (k < 7) nxt = rd(k + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        // A = dz1 for (co = li, windows 2g, 2g+1 of the K-step): the window's fp16 bits at its argmax
+        // slot, zero where ReLU blocks the gradient.  K order: dword 2 dr + wi = (window wi, row dr),
+        // halves dc = 0, 1, so slot (dr, dc) = code bits 0-1 is half-word 2 dr + dc of the 64-bit
+        // (row 1 | row 0) pair: ONE 64-bit shift by 16 * code.  The shift count is the byte << 4: the
+        // hardware takes its low 6 bits, which drops the ReLU bit.  The ReLU mask is bit 2 spread
+        // (v_bfe_i32).  (Selects per half-word cost ~10 VALU per window, this form ~6.)
+        u32x4 a4;
+#pragma unroll
+        for (int wi = 0; wi < 2; ++wi) {
+          const uint32_t ab = cur.ab[wi];
+          const uint32_t relu = (uint32_t)((int32_t)(ab << 29) >> 31);
+          const uint32_t hb = (wi ? cur.dpair >> 16 : cur.dpair & 0xFFFFu) & relu;
+          const uint64_t h64 = (uint64_t)hb << ((ab << 4) & 63u);
+          a4[wi] = (uint32_t)h64;
+          a4[2 + wi] = (uint32_t)(h64 >> 32);
+        }
+        const s16x8 ah = __builtin_bit_cast(s16x8, a4);
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk) acc[blk] = mfma_f16(ah, __builtin_bit_cast(s16x8, cur.b[blk]), acc[blk]);
+        __builtin_amdgcn_sched_barrier(0);
+        cur = nxt;
+      }
+    } else  // fp32 image: bf16x3, dz1 and x split hi + lo
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int rp = 2 * wv + h;
@@ -684,18 +850,6 @@ __global__ __launch_bounds__(256, L1B_WAVES) void l1_bwd_mfma_kernel(const void*
           // pooled columns 8sg + 2g + {0, 1}: column group 2sg + (g >> 1), pixels 2(g & 1) + {0, 1} --
           // one dword (a 32-lane half reads 32 consecutive words: conflict-free)
           const uint32_t dpair = dps[((rp * 8 + 2 * sg + (g >> 1)) * 16 + li) * 2 + (g & 1)];
-          if constexpr (H16) {  // fp16 bits at the argmax slot, zero where ReLU blocks the gradient;
-            // K order here: dword 2 dr + wi = (window wi, row dr), halves dc = 0, 1 (the B reads'
-            // order: ds_read2_b32 pairs (wi 0, 1) of one row land in consecutive registers)
-#pragma unroll
-            for (int wi = 0; wi < 2; ++wi) {
-              const uint32_t ab = ids[(rp * LB_PC + 8 * sg + 2 * g + wi) * 16 + li];
-              const uint32_t hb = (ab & 4u) ? ((dpair >> (16 * wi)) & 0xFFFFu) : 0u;
-              const uint32_t hs = hb << (16u * (ab & 1u));
-              hp[wi] = (ab & 2u) ? 0u : hs;
-              hp[2 + wi] = (ab & 2u) ? hs : 0u;
-            }
-          } else
 #pragma unroll
           for (int wi = 0; wi < 2; ++wi) {
             const int pp = rp * LB_PC + 8 * sg + 2 * g + wi;
@@ -716,13 +870,6 @@ __global__ __launch_bounds__(256, L1B_WAVES) void l1_bwd_mfma_kernel(const void*
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk) {
           const int bo = base + boff[blk];
-          if constexpr (H16) {  // dword 2 dr + wi = (window wi, row dr), cols dc = 0, 1: one pair word
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            const s16x8 bp = __builtin_bit_cast(
-                s16x8, u32x4{xs[bo], xs[bo + 2], xs[bo + LM_XS], xs[bo + LM_XS + 2]});
-            acc[blk] = mfma_f16(ah, bp, acc[blk]);
-            continue;
-          }
           uint32_t u[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
@@ -735,7 +882,7 @@ __global__ __launch_bounds__(256, L1B_WAVES) void l1_bwd_mfma_kernel(const void*
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             hp[j] = __builtin_amdgcn_perm(u[2 * j + 1], u[2 * j], 0x07060302u);
-            if constexpr (!LV) lp[j] = __builtin_amdgcn_perm(u[2 * j + 1], u[2 * j], 0x05040100u);
+            lp[j] = __builtin_amdgcn_perm(u[2 * j + 1], u[2 * j], 0x05040100u);
           }
           acc[blk] = mfma_bf16x3(ah, al, bh, bl, acc[blk]);
         }
