@@ -890,7 +890,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fused_head_backward(
     double scale, bool compute_dw, double update_lr, const c10::optional<Tensor>& dbfc_out,
     const c10::optional<Tensor>& dg_out, const c10::optional<Tensor>& dbe_out, bool keep_dw, int64_t c_begin,
     int64_t c_end, bool finalize, const c10::optional<Tensor>& g2m_out, const c10::optional<Tensor>& partial_out,
-    const c10::optional<Tensor>& mag, bool ypart_done) {
+    const c10::optional<Tensor>& mag, bool ypart_done, const c10::optional<Tensor>& mom_buf, double weight_decay,
+    double momentum, double dampening, bool nesterov, bool first_step) {
   TORCH_CHECK(ya.dim() == 3 && ya.size(1) == 32, "fused_head_backward: ya must be [B,32,PB]");
   const int64_t B = ya.size(0), Q = P / 2;
   TORCH_CHECK(Q >= 4 && B >= 1, "fused_head_backward: needs P/2 >= 4 pooled columns and B >= 1");
@@ -909,6 +910,31 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fused_head_backward(
   TORCH_CHECK(keep_dw || upd, "fused_head_backward: keep_dw=False needs update_lr > 0 (update-only step)");
   const bool whole = c_begin == 0 && c_end == 32;
   TORCH_CHECK(whole || !upd, "fused_head_backward: the fused SGD step runs on the whole weight only");
+  // mom_buf: the fused step is torch's SGD with momentum / weight decay (head_pb.hip MOM), the
+  // buffer updated in place beside the weight; everything is checked before anything is launched
+  const bool mom = mom_buf.has_value() && mom_buf->defined();
+  TORCH_CHECK(mom || (weight_decay == 0.0 && momentum == 0.0 && dampening == 0.0 && !nesterov && !first_step),
+              "fused_head_backward: weight_decay / momentum / dampening / nesterov / first_step need mom_buf");
+  TdsHeadMom hm{};
+  if (mom) {
+    TORCH_CHECK(upd, "fused_head_backward: the momentum step needs update_lr > 0");
+    TORCH_CHECK(whole && compute_dw && tds_head_bwd_pb_npass((int)B) == 1,
+                "fused_head_backward: the momentum step runs on the whole weight in one pass (<= 8 images)");
+    TORCH_CHECK(momentum > 0.0 && weight_decay >= 0.0, "fused_head_backward: mom_buf needs momentum > 0, weight_decay >= 0");
+    TORCH_CHECK(!nesterov || dampening == 0.0, "fused_head_backward: nesterov needs zero dampening");
+    need(*mom_buf, at::kFloat, {NC, 32 * Q * Q}, "mom_buf");
+    TORCH_CHECK(mom_buf->device() == wfc.device(), "fused_head_backward: mom_buf is on another device than fc.weight");
+    const char* w0 = static_cast<const char*>(wfc.data_ptr());
+    const char* m0 = static_cast<const char*>(mom_buf->data_ptr());
+    const int64_t nbytes = NC * 32 * Q * Q * (int64_t)sizeof(float);
+    TORCH_CHECK(m0 + nbytes <= w0 || w0 + nbytes <= m0, "fused_head_backward: mom_buf aliases fc.weight");
+    if (dw_out.has_value() && dw_out->defined() && keep_dw) {
+      const char* d0 = static_cast<const char*>(dw_out->data_ptr());
+      TORCH_CHECK(m0 + nbytes <= d0 || d0 + nbytes <= m0, "fused_head_backward: mom_buf aliases dw_out");
+    }
+    hm = TdsHeadMom{mom_buf->data_ptr<float>(), (float)weight_decay, (float)momentum, (float)dampening, nesterov, first_step};
+  }
+  const TdsHeadMom* hmp = mom ? &hm : nullptr;
   Tensor dW;  // undefined (None) for an update-only step
   if (!compute_dw) {
     dW = at::empty({0}, wfc.options());
@@ -967,7 +993,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fused_head_backward(
                                    dlogits.data_ptr<float>(), g2p, partial.data_ptr<double>(),
                                    compute_dw && dW.defined() ? dW.data_ptr<float>() : nullptr,
                                    upd ? const_cast<float*>(wfc.data_ptr<float>()) : nullptr, (int)B, (int)Q, (int)NC,
-                                   (float)scale, (float)update_lr, 0, 32, gp, g2inv, st, &hf);
+                                   (float)scale, (float)update_lr, 0, 32, gp, g2inv, st, &hf, hmp);
     TORCH_CHECK(rc == 0, "fused_head_backward: unsupported shape (rc ", rc, ")");
     check_launches("fused_head_backward");
     return {dW, dbfc, dgamma, dbeta, g2m, kbuf};
@@ -976,7 +1002,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fused_head_backward(
                                  dlogits.data_ptr<float>(), g2p, partial.data_ptr<double>(),
                                  compute_dw && dW.defined() ? dW.data_ptr<float>() : nullptr,
                                  upd ? const_cast<float*>(wfc.data_ptr<float>()) : nullptr, (int)B, (int)Q, (int)NC,
-                                 (float)scale, (float)update_lr, (int)c_begin, (int)c_end, gp, g2inv, st);
+                                 (float)scale, (float)update_lr, (int)c_begin, (int)c_end, gp, g2inv, st, nullptr, hmp);
   TORCH_CHECK(rc == 0, "fused_head_backward: unsupported shape (rc ", rc, ")");
   if (!finalize) {
     check_launches("fused_head_backward");
@@ -1317,7 +1343,9 @@ TORCH_LIBRARY_FRAGMENT(tdsa, m) {
       "int P, Tensor(a!)? dw_out, float scale, bool compute_dw=True, float update_lr=0.0, "
       "Tensor(b!)? dbfc_out=None, Tensor(c!)? dg_out=None, Tensor(d!)? dbe_out=None, bool keep_dw=True, "
       "int c_begin=0, int c_end=32, bool finalize=True, Tensor(f!)? g2m_out=None, Tensor(g!)? partial_out=None, "
-      "Tensor(h!)? mag=None, bool ypart_done=False) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
+      "Tensor(h!)? mag=None, bool ypart_done=False, Tensor(i!)? mom_buf=None, float weight_decay=0.0, "
+      "float momentum=0.0, float dampening=0.0, bool nesterov=False, bool first_step=False) "
+      "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
       &fused_head_backward);
   m.def(
       "fused_conv2_forward_bn(Tensor p1, Tensor wp, Tensor b2, Tensor? gamma2, Tensor? beta2, Tensor(a!)? rm2, "

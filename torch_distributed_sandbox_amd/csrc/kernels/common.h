@@ -252,4 +252,28 @@ __device__ __forceinline__ float4 g2m_planar4(const float* __restrict__ g2m, int
   return make_float4(g[0], g[QQ], g[2 * QQ], g[3 * QQ]);
 }
 
+// torch.optim.SGD's step with momentum and / or weight decay for one element (the flat sweep,
+// elementwise.hip, and the head backward's in-kernel step, head_pb.hip, share it, so both round
+// alike):
+//   d = g + wd w;  b' = first ? d : mom b + (1 - damp) d;  d = nesterov ? d + mom b' : b';  w' = w - lr d
+// omd = 1 - damp, formed on the host in fp32 (SgdRule::make).  fp32 roundings against the rule in
+// exact arithmetic on the fp32 hyperparameters: 4 into b' ((1), (2), (3) and omd), 2 more into w'
+// ((4), (5)); the tests' per-element bounds count them (tests/test_sgd_momentum_gpu.py).
+struct SgdRule {
+  float lr, wd, mom, omd;
+  int nesterov, first;  // first: this step creates the buffer (b' = d, the buffer is not read)
+  static SgdRule make(float lr, float wd, float mom, float damp, int nesterov, int first) {
+    return SgdRule{lr, wd, mom, 1.f - damp, nesterov, first};
+  }
+};
+// has_b: the rule keeps a buffer (mom != 0); without one only the weight decay applies
+__device__ __forceinline__ float sgd_rule_step(float w, float g, float b, const SgdRule& r, bool has_b, float& b_new) {
+  float d = r.wd != 0.f ? fmaf(r.wd, w, g) : g;                   // (1)
+  if (has_b) {
+    b_new = r.first ? d : fmaf(r.mom, b, r.omd * d);              // (2) omd d, (3) the sum
+    d = r.nesterov ? fmaf(r.mom, b_new, d) : b_new;               // (4)
+  }
+  return fmaf(-r.lr, d, w);                                       // (5)
+}
+
 }  // namespace tds

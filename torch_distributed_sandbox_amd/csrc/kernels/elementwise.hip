@@ -255,7 +255,35 @@ __global__ void sgd_multi_kernel(SgdChunkTable tab, float lr, float wd, float mo
   float* __restrict__ buf = tab.mom[ti];
   const int64_t n = tab.numel[ti];
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)buf)) & 15) == 0 && momentum == 0.f && wd == 0.f;
+  const bool al16 = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)buf)) & 15) == 0;  // (no buffer: nullptr)
+  const bool vec = al16 && momentum == 0.f && wd == 0.f;
+  // the momentum / weight-decay forms: one element's rule in common.h (sgd_rule_step), 16 bytes per
+  // access when every pointer allows it, with a scalar tail; misaligned slices take the scalar loop
+  const SgdRule rule = SgdRule{lr, wd, momentum, 1.f - dampening, nesterov, first_step};
+  const bool has_b = momentum != 0.f;
+  if (al16 && !vec) {
+    const int64_t n4 = n / 4;
+    float4* p4 = reinterpret_cast<float4*>(p);
+    const float4* g4 = reinterpret_cast<const float4*>(g);
+    float4* b4 = reinterpret_cast<float4*>(buf);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+      float4 a = p4[i], bo = make_float4(0.f, 0.f, 0.f, 0.f), bn = bo;
+      const float4 d = g4[i];
+      if (has_b && !first_step) bo = b4[i];
+      a.x = sgd_rule_step(a.x, d.x, bo.x, rule, has_b, bn.x);
+      a.y = sgd_rule_step(a.y, d.y, bo.y, rule, has_b, bn.y);
+      a.z = sgd_rule_step(a.z, d.z, bo.z, rule, has_b, bn.z);
+      a.w = sgd_rule_step(a.w, d.w, bo.w, rule, has_b, bn.w);
+      if (has_b) b4[i] = bn;
+      p4[i] = a;
+    }
+    for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+      float bn = 0.f;
+      p[i] = sgd_rule_step(p[i], g[i], has_b && !first_step ? buf[i] : 0.f, rule, has_b, bn);
+      if (has_b) buf[i] = bn;
+    }
+    return;
+  }
   if (vec) {
     const int64_t n4 = n / 4;
     float4* p4 = reinterpret_cast<float4*>(p);
@@ -270,14 +298,9 @@ __global__ void sgd_multi_kernel(SgdChunkTable tab, float lr, float wd, float mo
     return;
   }
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float d = g[i];
-    if (wd != 0.f) d += wd * p[i];
-    if (momentum != 0.f) {
-      float b = first_step ? d : momentum * buf[i] + (1.f - dampening) * d;
-      buf[i] = b;
-      d = nesterov ? d + momentum * b : b;
-    }
-    p[i] -= lr * d;
+    float bn = 0.f;
+    p[i] = sgd_rule_step(p[i], g[i], has_b && !first_step ? buf[i] : 0.f, rule, has_b, bn);
+    if (has_b) buf[i] = bn;
   }
 }
 

@@ -395,6 +395,7 @@ __global__ __launch_bounds__(256) void head_logits_kernel(const double* __restri
 //                                    dbeta2), then the same over the stored fp16 values (k2, k3)
 //   dW[j][c][pos] (= or +=) scale * sum_b dl[b][j] X[b][c][pos]      (WITH_DW; ACC adds)
 //   Wupd = W - lr * dW                                               (UPD: SGD step fused)
+//   Wupd, mbuf = torch's SGD rule with momentum / weight decay       (UPD && MOM, below)
 //   gpart (optional): this workgroup's max |g2m| as float bits (NaN-propagating as an unsigned
 //   max), at [(c*npass + pass)*nblk + band] -- reduced by the BN2-backward finalize into the
 //   magnitude bound behind the conv2 backward's fp16 scale (conv2_bwd.hip).  Plain stores: one
@@ -420,13 +421,34 @@ struct HBFin {
   uint32_t* mag;           // mag[32] <- max |g2m| (nullptr: no magnitude bound)
 };
 
-template <int NB, bool WITH_DW, bool ACC, bool UPD, bool KEEP = true>
+// MOM (with UPD): torch's SGD step with momentum / weight decay instead of the plain one (common.h
+// sgd_rule_step), the momentum buffer mbuf laid out like the weight and updated in place.  Its
+// 4-groups use the weight's addressing -- loaded at HPRow::ldoff, edge groups re-aligned as hp_fix_w
+// does, stored through hp_store4 inside nvalid only -- but per class, after g2m is formed and the ya
+// registers are dead, HP_MOM_AHEAD classes ahead of their use: all ten beside the weight's would
+// cost the third wave per SIMD (docs/KERNELS.md "Momentum in the head backward").
+constexpr int HP_MOM_AHEAD = 2;
+
+// one loaded buffer 4-group re-aligned like the weight's (hp_fix_w); what lies outside the image is
+// never stored
+__device__ __forceinline__ float4 hp_fix_b(float4 b, int sh) {
+  if (__builtin_amdgcn_ballot_w64(sh != 0) == 0) return b;
+  const float e[4] = {b.x, b.y, b.z, b.w};
+  float o[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) o[k] = (sh > 0 && k + sh >= 4) ? 0.f : e[(k + sh) & 3];
+  return make_float4(o[0], o[1], o[2], o[3]);
+}
+
+// (mbuf and rule are trailing arguments the other instantiations never read: their code is what it
+// was before the momentum form existed)
+template <int NB, bool WITH_DW, bool ACC, bool UPD, bool KEEP = true, bool MOM = false>
 __global__ __launch_bounds__(HP_THREADS) void head_bwd_pb_kernel(
     const unsigned short* __restrict__ ya, TdsYaDec yd, const float* W, const float* __restrict__ aff2,
     const float* __restrict__ dl,
     unsigned short* __restrict__ g2h, double* __restrict__ partial, float* dW, float* Wupd, PBGeom g, int b0, int pass,
     int npass, int NC, float scale, float lr, int c0, uint32_t* __restrict__ gpart, HBFin fin,
-    const uint32_t* __restrict__ wmaxp, int wrows, int Btot, float* __restrict__ g2inv) {
+    const uint32_t* __restrict__ wmaxp, int wrows, int Btot, float* __restrict__ g2inv, float* mbuf, SgdRule rule) {
   __shared__ float red[4][HP_THREADS / 64];
   __shared__ uint32_t wms[10];
   __shared__ float g2sc;
@@ -526,8 +548,23 @@ __global__ __launch_bounds__(HP_THREADS) void head_bwd_pb_kernel(
     }
     if constexpr (WITH_DW) {
       const HPRow& rw = rwg;
+      // the momentum buffer's groups, HP_MOM_AHEAD classes ahead (a creating step reads none);
+      // the load of class j + HP_MOM_AHEAD precedes the stores of class j in program order
+      [[maybe_unused]] float4 mb[HP_MOM_AHEAD];
+      [[maybe_unused]] const int64_t cls = (int64_t)32 * Q * (int64_t)Q;
+      if constexpr (MOM) {
+#pragma unroll
+        for (int j = 0; j < HP_MOM_AHEAD; ++j)
+          mb[j] = rule.first ? make_float4(0.f, 0.f, 0.f, 0.f) : hp_ld4(mbuf + (j < NC ? j : 0) * cls + rw.ldoff);
+      }
 #pragma unroll
       for (int j = 0; j < 10; ++j) {
+        [[maybe_unused]] float4 bcur;
+        if constexpr (MOM) {
+          bcur = mb[j % HP_MOM_AHEAD];
+          if (j + HP_MOM_AHEAD < 10 && !rule.first)
+            mb[j % HP_MOM_AHEAD] = hp_ld4(mbuf + (j + HP_MOM_AHEAD < NC ? j + HP_MOM_AHEAD : 0) * cls + rw.ldoff);
+        }
         if (j < NC) {
           float s[4];
 #pragma unroll
@@ -547,7 +584,16 @@ __global__ __launch_bounds__(HP_THREADS) void head_bwd_pb_kernel(
             }
           } else {
             if constexpr (KEEP) hp_store4(dW, g, rw, j, d);
-            if constexpr (UPD) {  // torch SGD: p -= lr * g
+            if constexpr (UPD && MOM) {  // torch SGD with momentum / weight decay
+              const float4 w = cur.w[j], bo = hp_fix_b(bcur, rw.sh);
+              float4 bn, wn;
+              wn.x = sgd_rule_step(w.x, d.x, bo.x, rule, true, bn.x);
+              wn.y = sgd_rule_step(w.y, d.y, bo.y, rule, true, bn.y);
+              wn.z = sgd_rule_step(w.z, d.z, bo.z, rule, true, bn.z);
+              wn.w = sgd_rule_step(w.w, d.w, bo.w, rule, true, bn.w);
+              hp_store4(mbuf, g, rw, j, bn);
+              hp_store4(Wupd, g, rw, j, wn);
+            } else if constexpr (UPD) {  // torch SGD: p -= lr * g
               const float4 w = cur.w[j];
               hp_store4(Wupd, g, rw, j, make_float4(w.x - lr * d.x, w.y - lr * d.y, w.z - lr * d.z, w.w - lr * d.w));
             }
@@ -992,8 +1038,11 @@ int tds_head_bwd_pb_npass(int B) { return (B + HP_MAXB - 1) / HP_MAXB; }
 
 int tds_head_bwd_pb(const unsigned short* ya, TdsYaDec yd, const float* Wfc, const float* aff2, const float* dlogits, unsigned short* g2m,
                     double* partial, float* dW, float* Wupd, int B, int Q, int NC, float scale, float lr, int c0,
-                    int c1, uint32_t* gpart, float* g2inv, hipStream_t st, const TdsHeadBwdFin* hf) {
+                    int c1, uint32_t* gpart, float* g2inv, hipStream_t st, const TdsHeadBwdFin* hf, const TdsHeadMom* hm) {
   if (B < 1 || NC < 1 || NC > 10 || Q < 1 || c0 < 0 || c1 > 32 || c0 >= c1) return -1;
+  // the momentum step: the in-place update of the whole weight in one image pass, nothing else
+  if (hm != nullptr && (hm->buf == nullptr || Wupd == nullptr || !(lr > 0.f) || B > HP_MAXB || c0 != 0 || c1 != 32))
+    return -6;
   const uint32_t* wmaxp = hp_wmax_buf(Q, st);
   if (wmaxp == nullptr) return -5;
   const int wrows = hp_grid(pb_geom(Q)).per_channel();
@@ -1018,6 +1067,29 @@ int tds_head_bwd_pb(const unsigned short* ya, TdsYaDec yd, const float* Wfc, con
     fin.mag = hf->mag;
   }
   const int nwg = (c1 - c0) * hp_grid_b(g).per_channel();
+  if (hm != nullptr) {
+    const SgdRule rule = SgdRule::make(lr, hm->wd, hm->momentum, hm->dampening, hm->nesterov ? 1 : 0, hm->first_step ? 1 : 0);
+#define TDS_HPM_E(NBV, KP)                                                                                             \
+  hipLaunchKernelGGL((head_bwd_pb_kernel<NBV, true, false, true, KP, true>), dim3(nwg), dim3(HP_THREADS), 0, st, ya, yd, \
+                     Wfc, aff2, dlogits, g2m, partial, dW, Wupd, g, 0, 0, 1, NC, scale, lr, 0, gpart, fin, wmaxp, wrows, B, \
+                     g2inv, hm->buf, rule);
+#define TDS_HPM(NBV)            \
+  case NBV:                     \
+    if (dW) {                   \
+      TDS_HPM_E(NBV, true)      \
+    } else {                    \
+      TDS_HPM_E(NBV, false)     \
+    }                           \
+    TDS_LAUNCH_CHECK();         \
+    break;
+    switch (B) {
+      TDS_HPM(1) TDS_HPM(2) TDS_HPM(3) TDS_HPM(4) TDS_HPM(5) TDS_HPM(6) TDS_HPM(7) TDS_HPM(8)
+      default: return -1;
+    }
+#undef TDS_HPM
+#undef TDS_HPM_E
+    return 0;
+  }
   for (int pass = 0; pass < npass; ++pass) {
     const int b0 = pass * HP_MAXB;
     const int nb = B - b0 < HP_MAXB ? B - b0 : HP_MAXB;
@@ -1025,7 +1097,7 @@ int tds_head_bwd_pb(const unsigned short* ya, TdsYaDec yd, const float* Wfc, con
 #define TDS_HPB_E(NBV, WD, AC, UP, KP)                                                                             \
   hipLaunchKernelGGL((head_bwd_pb_kernel<NBV, WD, AC, UP, KP>), dim3(nwg), dim3(HP_THREADS), 0, st, ya, yd, Wfc, aff2, \
                      dlogits, g2m, partial, dW, Wupd, g, b0, pass, npass, NC, scale, lr, c0, gpart, fin, wmaxp, wrows, \
-                     B, g2inv);
+                     B, g2inv, nullptr, SgdRule{});
 #define TDS_HPB(NBV)                                   \
   case NBV:                                            \
     if (!dW && Wupd) {                                 \

@@ -265,9 +265,18 @@ struct TdsHeadBwdFin {
 };
 // g2m: fp16 [B][32][Q][Q] at a per-channel power-of-two scale 2^e_c (g2inv[c] <- 2^-e_c), bounded
 // by the max |W| per channel and class that the last head forward on this stream measured
+// hm (optional): the fused step is torch's SGD with momentum / weight decay (common.h sgd_rule_step)
+// on the momentum buffer buf ([NC][32*Q*Q] like the weight, updated in place; first_step: created by
+// this step, its contents ignored).  Needs Wupd, lr > 0, B <= 8 and all 32 channels: -6 otherwise.
+struct TdsHeadMom {
+  float* buf;
+  float wd, momentum, dampening;
+  bool nesterov, first_step;
+};
 int tds_head_bwd_pb(const unsigned short* ya, TdsYaDec yd, const float* Wfc, const float* aff2, const float* dlogits, unsigned short* g2m,
                     double* partial, float* dW, float* Wupd, int B, int Q, int NC, float scale, float lr, int c0,
-                    int c1, uint32_t* gpart, float* g2inv, hipStream_t st, const TdsHeadBwdFin* hf = nullptr);
+                    int c1, uint32_t* gpart, float* g2inv, hipStream_t st, const TdsHeadBwdFin* hf = nullptr,
+                    const TdsHeadMom* hm = nullptr);
 
 // ---- zs_exchange.hip (zero-suppressed fc-input rows, parallel/zs.py)
 int64_t tds_zs_npages(int64_t n);

@@ -143,6 +143,10 @@ void sgd_step_(at::TensorList params, at::TensorList grads, at::TensorList moms,
       check_f32_dev(params[i], "param");
       check_f32_dev(grads[i], "grad");
       TORCH_CHECK(params[i].numel() == grads[i].numel(), "tdsa.sgd_step_: param/grad numel mismatch");
+      if (momentum != 0.0) {
+        check_f32_dev(moms[i], "momentum buffer");
+        TORCH_CHECK(moms[i].numel() == params[i].numel(), "tdsa.sgd_step_: param/momentum buffer numel mismatch");
+      }
       tab.param[tab.n] = params[i].data_ptr<float>();
       tab.grad[tab.n] = grads[i].data_ptr<float>();
       tab.mom[tab.n] = momentum != 0.0 ? moms[i].data_ptr<float>() : nullptr;

@@ -432,9 +432,16 @@ class _Head(torch.autograd.Function):
         else:
             # world size 1 under DDP(overlap_optimizer): the SGD step of the fc weight runs in
             # this same kernel (ops/fused_update.py)
-            lr = None
+            lr, mom_args = None, ()
             if ctx.needs_input_grad[12] and ya.shape[0] <= 8:  # one pass of head_bwd_pb_kernel
-                lr = fused_update.take(ctx.wfc_param)
+                step = fused_update.take_step(ctx.wfc_param)
+                if step is not None and step["buf"] is not None:
+                    # momentum / weight decay: the kernel's momentum form steps the buffer in place too
+                    lr = step["lr"]
+                    mom_args = (step["buf"], step["weight_decay"], step["momentum"], step["dampening"],
+                                step["nesterov"], step["first_step"])
+                else:
+                    lr = step["lr"] if step is not None else fused_update.take(ctx.wfc_param)
             keep = not lr or fused_update.keep_grad(ctx.wfc_param)
             # the gradient's destination (DDP's bucket slot) only when a gradient is written: an
             # update-only step never requests the slot, so DDP never allocates it (ddp.py _lazy_from)
@@ -443,7 +450,8 @@ class _Head(torch.autograd.Function):
             dW, dbfc, dg2, dbe2, g2m, kbuf = ops.fused_head_backward(dlogits, ya, stats2, aff2, b2, g2, wfc, P,
                                                                      dw_out if keep else None, 1.0, True,
                                                                      float(lr or 0.0), dbfc_o, dg_o, dbe_o, keep,
-                                                                     mag=ctx.link.mag, ypart_done=ctx.link.bn_done)
+                                                                     0, 32, True, None, None, ctx.link.mag,
+                                                                     ctx.link.bn_done, *mom_args)
             if lr:
                 # update-only step: no gradient for the weight (dW is None), as in torch's
                 # optimizer-in-backward; the owner marks the parameter ready

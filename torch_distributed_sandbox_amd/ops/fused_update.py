@@ -15,6 +15,10 @@ False)``) it is not materialised -- ``param.grad`` stays None, the semantics of 
 optimizer-in-backward -- and the kernel writes only the updated weight (720 MB less HBM
 traffic per step at 3000²).  With ``keep_fused_grads=True`` the gradient is also written
 to ``param.grad`` (the DDP bucket).
+
+Momentum, dampening, weight decay, nesterov: the head backward's momentum form applies torch's
+whole rule and steps the parameter's momentum buffer in place (:func:`take_step`; kernels/head_pb.hip
+MOM).  The exchanges' in-place step stays plain-SGD only (:func:`take`).
 """
 from __future__ import annotations
 
@@ -23,7 +27,8 @@ _ATTR = "_tds_fused_update"
 
 def register(param, provider) -> None:
     """``provider("query")`` returns the learning rate to apply now (or None);
-    ``provider("applied")`` records that the backward applied it."""
+    ``provider("query_step")`` the whole step (:func:`take_step`; a provider that does not know
+    the query returns None); ``provider("applied")`` records that the backward applied it."""
     setattr(param, _ATTR, provider)
 
 
@@ -45,6 +50,22 @@ def take(param, exchanged: bool = False):
     if fn is None:
         return None
     return fn("query_exchange" if exchanged else "query")
+
+
+def take_step(param):
+    """The whole step for an in-backward update of ``param`` by the kernel that produces the LOCAL
+    gradient (world size 1), or None: a dict with ``lr``, ``momentum``, ``dampening``,
+    ``weight_decay``, ``nesterov``, ``buf`` (the parameter's momentum buffer, updated in place by
+    the kernel; None without momentum) and ``first_step`` (this step creates the buffer, its
+    contents are to be ignored).  :func:`take` stays the plain-SGD query: a group with momentum or
+    weight decay answers it with None, so the exchanged paths (parallel/factored.py) keep writing
+    the gradient and the optimizer applies the step."""
+    if param is None:
+        return None
+    fn = getattr(param, _ATTR, None)
+    if fn is None:
+        return None
+    return fn("query_step")
 
 
 def keep_grad(param) -> bool:

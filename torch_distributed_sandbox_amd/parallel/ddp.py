@@ -624,12 +624,22 @@ class DistributedDataParallel(nn.Module):
                     # only a plain synchronised step whose gradient lands straight in the bucket;
                     # a local gradient ("query") only at world size 1, the exchange's averaged one
                     # ("query_exchange", parallel/factored.py) at any world size
-                    if what == "query" and self.world_size != 1:
+                    if what not in ("query", "query_exchange", "query_step"):
+                        return None
+                    if what in ("query", "query_step") and self.world_size != 1:
                         return None
                     if what == "query_exchange" and self.keep_fused_grads:
                         return None
                     if not self.require_backward_grad_sync or p.grad is not None or id(p) in self._fused_done:
                         return None
+                    if what == "query_step":
+                        # the whole step, momentum and weight decay included (one group, no maximize:
+                        # the optimizer checks); a weight-decay-only group has no buffer for the
+                        # kernel's momentum form and keeps the optimizer's sweep
+                        step = optimizer.fused_step(p) if hasattr(optimizer, "fused_step") else None
+                        if step is not None and step["buf"] is None and plain_sgd_lr() is None:
+                            return None
+                        return step
                     return plain_sgd_lr()
 
                 fused_update.register(p, provider)

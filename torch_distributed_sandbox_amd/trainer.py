@@ -39,6 +39,10 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--image-size", default=3000, type=int, help="square image edge (reference: 3000)")
     p.add_argument("--batch-size", default=5, type=int, help="per-GPU batch size (reference: 5)")
     p.add_argument("--lr", default=1e-4, type=float)
+    p.add_argument("--momentum", default=0.0, type=float, help="SGD momentum (0: plain SGD, the reference)")
+    p.add_argument("--weight-decay", default=0.0, type=float, help="SGD weight decay")
+    p.add_argument("--dampening", default=0.0, type=float, help="SGD dampening of the momentum")
+    p.add_argument("--nesterov", action="store_true", help="Nesterov momentum (needs --momentum > 0, no dampening)")
     p.add_argument("--max-steps", default=0, type=int, help="stop after this many steps per epoch (0 = full epoch)")
     p.add_argument("--dataset-size", default=60000, type=int, help="synthetic MNIST size (reference: 60000)")
     p.add_argument("--log-interval", default=100, type=int)
@@ -187,7 +191,9 @@ def train(gpu: int, args, distributed: bool = False) -> dict:
     model = ConvNet(image_shape=(H, W), device=device, mode=args.mode)
     batch_size = args.batch_size
     criterion = CrossEntropyLoss()
-    optimizer = SGD(model.parameters(), args.lr)
+    opt_args = {"momentum": float(getattr(args, "momentum", 0.0)), "weight_decay": float(getattr(args, "weight_decay", 0.0)),
+                "dampening": float(getattr(args, "dampening", 0.0)), "nesterov": bool(getattr(args, "nesterov", False))}
+    optimizer = SGD(model.parameters(), args.lr, **opt_args)
     if distributed or device.type == "cuda":
         # the tuned plan bench.py measures, also for the single-GPU script: at world size 1 the
         # wrapper owns the flat parameter / gradient buffers (one SGD sweep over the small
@@ -269,6 +275,7 @@ def train(gpu: int, args, distributed: bool = False) -> dict:
     t_end = time.perf_counter()
     summary = {"rank": rank, "world_size": world, "steps": steps_done, "batch_size": batch_size,
                "image_size": H, "final_loss": float(loss.item()) if loss is not None else None,
+               "lr": float(args.lr), **opt_args,
                "plan": (f"DDP wrapper ({getattr(model, 'reducer_kind', '?')} reducer, fc grad "
                         f"{model.fc_grad_path()}, overlap_optimizer={model.overlap_optimizer})"
                         if isinstance(model, DistributedDataParallel) else "plain module"),

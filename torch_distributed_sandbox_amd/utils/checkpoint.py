@@ -50,5 +50,5 @@ def load(path: str, model, optimizer=None, map_location=None, broadcast: bool = 
                 for t in list(m.parameters()) + [b for b in m.buffers() if b is not None]:
                     tdist.broadcast(t.data, 0)
     if state.get("torch_rng") is not None:
-        torch.set_rng_state(state["torch_rng"])
+        torch.set_rng_state(state["torch_rng"].cpu())  # (map_location may have moved it to the GPU)
     return int(state.get("step", 0)), int(state.get("epoch", 0)), state.get("extra", {})
