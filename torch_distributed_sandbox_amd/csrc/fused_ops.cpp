@@ -549,86 +549,147 @@ void eval_metrics(const Tensor& logits, const Tensor& labels, const Tensor& acc)
   check_launches("eval_metrics");
 }
 
-// The head forward on a finished BN2 affine (fused_conv2_forward_bn's aff2): logits only, finished
-// inside the head's launch (head_pb.hip HPFin) for B <= 8
+// ---------------------------------------------------------------- fused head: BN2 + ReLU + pool + fc over ya
+// What every head op checks of ya and fc.weight [NC <= 10, 32 Q Q].  ya is [B, 32, PB] fp16; for the
+// pooled updates the ranks' planes [W, B, nch, PB] (`ranked`: that argument's name).  one_pass: at
+// most 8 images, one image pass of the head kernels.
+struct HeadDims {
+  int64_t B, Q, NC;
+  int64_t K() const { return 32 * Q * Q; }
+};
+HeadDims head_dims(const Tensor& ya, const Tensor& wfc, int64_t P, const char* who, bool one_pass = false,
+                   int64_t nch = 32, const char* ranked = nullptr) {
+  const int64_t lead = ranked ? 1 : 0, Q = P / 2;
+  const char* name = ranked ? ranked : "ya";
+  TORCH_CHECK(ya.dim() == 3 + lead && ya.size(1 + lead) == nch, who, ": ", name, " must be [", ranked ? "W," : "", "B,",
+              nch, ",PB]");
+  const int64_t B = ya.size(lead);
+  TORCH_CHECK(Q >= 4 && B >= 1 && (!one_pass || tds_head_bwd_pb_npass((int)B) == 1), who,
+              ": needs P/2 >= 4 pooled columns and B >= 1", one_pass ? " (<= 8 images: one pass)" : "");
+  std::vector<int64_t> shape{B, nch, pb_plane(P)};
+  if (ranked) shape.insert(shape.begin(), ya.size(0));
+  need(ya, at::kHalf, shape, name);
+  TORCH_CHECK(wfc.dim() == 2 && wfc.size(1) == 32 * Q * Q && wfc.size(0) >= 1 && wfc.size(0) <= 10, who,
+              ": fc.weight must be [<=10, 32*Q*Q]");
+  need(wfc, at::kFloat, {wfc.size(0), 32 * Q * Q}, "fc.weight");
+  return {B, Q, wfc.size(0)};
+}
+
+// x_out: where a forward writes its fc input rows X [B, cols] (the activation exchange sends them)
+float* x_out_rows(const c10::optional<Tensor>& x_out, int64_t B, int64_t cols) {
+  if (!x_out.has_value() || !x_out->defined()) return nullptr;
+  need(*x_out, at::kFloat, {B, cols}, "x_out (fc input rows)");
+  return x_out->data_ptr<float>();
+}
+
+// The head forward's workspace, in head_forward_range_ws's order: per-workgroup partials (the last 32
+// rows: the in-launch finalizer's channel sums) and logit sums in fp64, the logits, and what the
+// cross-entropy writes.  The first n of them: the caller's (`given`, checked) or fresh ones.
+enum { WS_PART, WS_LSUM, WS_LOGITS, WS_DLOGITS, WS_LOSS, WS_INV, WS_ALL };
+std::vector<Tensor> head_ws(const Tensor& like, const HeadDims& d, int n, const std::vector<Tensor>* given = nullptr) {
+  const char* const name[WS_ALL] = {"head partials", "logit sums", "logits", "dlogits", "loss", "1/count"};
+  const int64_t BN = d.B * d.NC, nblk = 32 * tds_head_pb_nblk((int)d.Q);
+  const std::vector<int64_t> shape[WS_ALL] = {{(nblk + 32) * BN}, {BN}, {d.B, d.NC}, {d.B, d.NC}, {}, {1}};
+  std::vector<Tensor> ws;
+  ws.reserve(n);
+  for (int i = 0; i < n; ++i) {
+    const at::ScalarType dt = i <= WS_LSUM ? at::kDouble : at::kFloat;
+    if (given) need((*given)[i], dt, shape[i], name[i]);
+    ws.push_back(given ? (*given)[i] : at::empty(shape[i], like.options().dtype(dt)));
+  }
+  return ws;
+}
+
+// The head forward of all four ops, and the one call of tds_head_fwd_pb (kernels/head_pb.hip): checks,
+// workspace, the launch of channels [c0, c1), returns the workspace.  The logits are finished inside the
+// launch that completes the 32nd channel (HPFin) for B <= 8, by a launch of their own otherwise.
+// aff2(): the BN2 affine's 64 floats, asked for once every check has passed (fused_head_forward
+// finalizes BN2 there).  labels add the mean cross-entropy loss (torch's CrossEntropyLoss defaults:
+// ignore_index -100, no label smoothing) and dlogits, formed by the finalizing workgroup right after
+// the logits (ce_small.h) -- one launch fewer than logits then ops.cross_entropy, with the same
+// arithmetic.  given: the range form's shared workspace, for at most 8 images.
+template <class Aff>
+std::vector<Tensor> head_fwd(const char* who, const Tensor& ya, const Tensor& b2, const c10::optional<Tensor>& mag,
+                             const Tensor& wfc, const c10::optional<Tensor>& bfc, int64_t P,
+                             const c10::optional<Tensor>& x_out, Aff&& aff2, const c10::optional<Tensor>& labels = {},
+                             const std::vector<Tensor>* given = nullptr, int64_t c0 = 0, int64_t c1 = 32) {
+  TORCH_CHECK(0 <= c0 && c0 < c1 && c1 <= 32, who, ": channels 0 <= c0 < c1 <= 32");
+  const HeadDims d = head_dims(ya, wfc, P, who, given != nullptr);
+  const float* bf = optf(bfc, d.NC, "fc.bias");
+  float* xo = x_out_rows(x_out, d.B, (c1 - c0) * d.Q * d.Q);
+  const TdsYaDec yd = ya_dec(b2, mag);
+  const int64_t* lab = nullptr;
+  if (labels.has_value() && labels->defined()) {
+    need(*labels, at::kLong, {d.B}, "labels");
+    TORCH_CHECK(labels->device() == ya.device(), who, ": labels must be on ya's device");
+    lab = labels->data_ptr<int64_t>();
+  }
+  c10::DeviceGuard guard(ya.device());
+  hipStream_t st = stream_of(ya);
+  const float* aff = aff2();
+  const auto ws = head_ws(ya, d, given || lab ? WS_ALL : WS_DLOGITS, given);
+  auto f32 = [&](size_t i) { return i < ws.size() ? ws[i].data_ptr<float>() : nullptr; };
+  const int rc = tds_head_fwd_pb(ya_out(ya), yd, wfc.data_ptr<float>(), bf, aff, ws[WS_PART].data_ptr<double>(),
+                                 ws[WS_LSUM].data_ptr<double>(), f32(WS_LOGITS), xo, (int)d.B, (int)d.Q, (int)d.NC, st,
+                                 true, lab, f32(WS_DLOGITS), f32(WS_LOSS), f32(WS_INV), (int)c0, (int)c1);
+  TORCH_CHECK(rc >= 0, who, ": unsupported shape (a channel range needs the in-launch finalize: not TDS_FUSED_FIN=0)");
+  if (rc == 0 && lab) {  // (the finalizer was not in the launch: the separate CE)
+    auto row_loss = at::empty({d.B}, ya.options().dtype(at::kFloat));
+    tds_cross_entropy(f32(WS_LOGITS), lab, row_loss.data_ptr<float>(), f32(WS_DLOGITS), f32(WS_LOSS), f32(WS_INV),
+                      (int)d.B, (int)d.NC, -100, 0.f, st);
+  }
+  check_launches(who);
+  return ws;
+}
+auto finished_aff(const Tensor& aff2) {  // (fused_conv2_forward_bn's)
+  need(aff2, at::kFloat, {64}, "aff2");
+  return [&aff2] { return aff2.data_ptr<float>(); };
+}
+
+// BN2 finalized here from the conv2 forward's partials, then the head forward.
+// returns (logits, stats2 [mean32|invstd32], aff2 [a32|b32])
+std::tuple<Tensor, Tensor, Tensor> fused_head_forward(
+    const Tensor& ya, const Tensor& partial2, const Tensor& b2, const c10::optional<Tensor>& gamma2,
+    const c10::optional<Tensor>& beta2, const c10::optional<Tensor>& rm2, const c10::optional<Tensor>& rv2,
+    const c10::optional<Tensor>& nbt2, double momentum, double eps, const Tensor& wfc, const c10::optional<Tensor>& bfc,
+    int64_t P, const c10::optional<Tensor>& x_out, const c10::optional<Tensor>& mag) {
+  TORCH_CHECK(partial2.is_cuda() && partial2.scalar_type() == at::kDouble && partial2.numel() % 64 == 0, "partial2");
+  const int nch = (int)(partial2.numel() / 64);
+  const float* g = optf(gamma2, 32, "bn2.weight");
+  const float* be = optf(beta2, 32, "bn2.bias");
+  float* rm = const_cast<float*>(optf(rm2, 32, "bn2.running_mean"));
+  float* rv = const_cast<float*>(optf(rv2, 32, "bn2.running_var"));
+  int64_t* nb = nullptr;
+  if (nbt2.has_value() && nbt2->defined()) {
+    TORCH_CHECK(nbt2->is_cuda() && nbt2->scalar_type() == at::kLong && nbt2->numel() == 1, "bn2.num_batches_tracked");
+    nb = nbt2->data_ptr<int64_t>();
+  }
+  Tensor stats, aff;
+  const auto ws = head_fwd("fused_head_forward", ya, b2, mag, wfc, bfc, P, x_out, [&] {
+    stats = at::empty({64}, ya.options().dtype(at::kFloat));
+    aff = at::empty({64}, ya.options().dtype(at::kFloat));
+    tds_bn_reduce_finalize(partial2.data_ptr<double>(), 32, nch, ya.size(0) * P * P, b2.data_ptr<float>(), (float)eps,
+                           (float)momentum, g, be, stats.data_ptr<float>(), rm, rv, nb, aff.data_ptr<float>(),
+                           stream_of(ya));
+    return aff.data_ptr<float>();
+  });
+  return {ws[WS_LOGITS], stats, aff};
+}
+
+// The head forward on a finished BN2 affine: logits only
 Tensor fused_head_forward_aff(const Tensor& ya, const Tensor& aff2, const Tensor& b2, const c10::optional<Tensor>& mag,
                               const Tensor& wfc, const c10::optional<Tensor>& bfc, int64_t P,
                               const c10::optional<Tensor>& x_out) {
-  TORCH_CHECK(ya.dim() == 3 && ya.size(1) == 32, "fused_head_forward_aff: ya must be [B,32,PB]");
-  const int64_t B = ya.size(0), Q = P / 2;
-  TORCH_CHECK(Q >= 4 && B >= 1, "fused_head_forward_aff: needs P/2 >= 4 pooled columns and B >= 1");
-  need(ya, at::kHalf, {B, 32, pb_plane(P)}, "ya (fp16)");
-  need(aff2, at::kFloat, {64}, "aff2");
-  TORCH_CHECK(wfc.dim() == 2 && wfc.size(1) == 32 * Q * Q && wfc.size(0) >= 1 && wfc.size(0) <= 10,
-              "fc.weight must be [<=10, 32*Q*Q]");
-  const int64_t NC = wfc.size(0);
-  need(wfc, at::kFloat, {NC, 32 * Q * Q}, "fc.weight");
-  const float* bf = optf(bfc, NC, "fc.bias");
-  float* xo = nullptr;
-  if (x_out.has_value() && x_out->defined()) {
-    need(*x_out, at::kFloat, {B, 32 * Q * Q}, "x_out (fc input rows)");
-    xo = x_out->data_ptr<float>();
-  }
-  c10::DeviceGuard guard(ya.device());
-  const int nblk = 32 * tds_head_pb_nblk((int)Q);
-  auto part = at::empty({(int64_t)(nblk + 32) * B * NC}, ya.options().dtype(at::kDouble));
-  auto lsum = at::empty({B * NC}, ya.options().dtype(at::kDouble));
-  auto logits = at::empty({B, NC}, ya.options().dtype(at::kFloat));
-  const int rc = tds_head_fwd_pb(ya_out(ya), ya_dec(b2, mag), wfc.data_ptr<float>(), bf, aff2.data_ptr<float>(),
-                                 part.data_ptr<double>(), lsum.data_ptr<double>(), logits.data_ptr<float>(), xo, (int)B,
-                                 (int)Q, (int)NC, stream_of(ya));
-  TORCH_CHECK(rc == 0, "fused_head_forward_aff: unsupported shape");
-  check_launches("fused_head_forward_aff");
-  return logits;
+  return head_fwd("fused_head_forward_aff", ya, b2, mag, wfc, bfc, P, x_out, finished_aff(aff2))[WS_LOGITS];
 }
 
-// fused_head_forward_aff with the batch's labels: the mean cross-entropy loss (torch's
-// CrossEntropyLoss defaults: ignore_index -100, no label smoothing) and dlogits formed by the
-// head forward's finalizing workgroup right after the logits (ce_small.h) -- one launch fewer than
-// logits then ops.cross_entropy, with the same arithmetic.  Returns (logits, loss, dlogits).
+// The same with the batch's labels: returns (logits, loss, dlogits)
 std::tuple<Tensor, Tensor, Tensor> fused_head_forward_aff_ce(const Tensor& ya, const Tensor& aff2, const Tensor& b2,
                                                              const c10::optional<Tensor>& mag, const Tensor& wfc,
                                                              const c10::optional<Tensor>& bfc, int64_t P,
                                                              const Tensor& labels, const c10::optional<Tensor>& x_out) {
-  TORCH_CHECK(ya.dim() == 3 && ya.size(1) == 32, "fused_head_forward_aff_ce: ya must be [B,32,PB]");
-  const int64_t B = ya.size(0), Q = P / 2;
-  TORCH_CHECK(Q >= 4 && B >= 1, "fused_head_forward_aff_ce: needs P/2 >= 4 pooled columns and B >= 1");
-  need(ya, at::kHalf, {B, 32, pb_plane(P)}, "ya (fp16)");
-  need(aff2, at::kFloat, {64}, "aff2");
-  TORCH_CHECK(wfc.dim() == 2 && wfc.size(1) == 32 * Q * Q && wfc.size(0) >= 1 && wfc.size(0) <= 10,
-              "fc.weight must be [<=10, 32*Q*Q]");
-  const int64_t NC = wfc.size(0);
-  need(wfc, at::kFloat, {NC, 32 * Q * Q}, "fc.weight");
-  need(labels, at::kLong, {B}, "labels");
-  TORCH_CHECK(labels.device() == ya.device(), "fused_head_forward_aff_ce: labels must be on ya's device");
-  const float* bf = optf(bfc, NC, "fc.bias");
-  float* xo = nullptr;
-  if (x_out.has_value() && x_out->defined()) {  // (the activation exchange's fc input rows)
-    need(*x_out, at::kFloat, {B, 32 * Q * Q}, "x_out (fc input rows)");
-    xo = x_out->data_ptr<float>();
-  }
-  c10::DeviceGuard guard(ya.device());
-  hipStream_t st = stream_of(ya);
-  const int nblk = 32 * tds_head_pb_nblk((int)Q);
-  auto part = at::empty({(int64_t)(nblk + 32) * B * NC}, ya.options().dtype(at::kDouble));
-  auto lsum = at::empty({B * NC}, ya.options().dtype(at::kDouble));
-  auto logits = at::empty({B, NC}, ya.options().dtype(at::kFloat));
-  auto dlogits = at::empty({B, NC}, ya.options().dtype(at::kFloat));
-  auto loss = at::empty({}, ya.options().dtype(at::kFloat));
-  auto inv = at::empty({1}, ya.options().dtype(at::kFloat));
-  const int rc = tds_head_fwd_pb(ya_out(ya), ya_dec(b2, mag), wfc.data_ptr<float>(), bf, aff2.data_ptr<float>(),
-                                 part.data_ptr<double>(), lsum.data_ptr<double>(), logits.data_ptr<float>(), xo,
-                                 (int)B, (int)Q, (int)NC, st, true, labels.data_ptr<int64_t>(),
-                                 dlogits.data_ptr<float>(), loss.data_ptr<float>(), inv.data_ptr<float>());
-  TORCH_CHECK(rc >= 0, "fused_head_forward_aff_ce: unsupported shape");
-  if (rc == 0) {  // (the finalizer was not in the launch: the separate CE)
-    auto row_loss = at::empty({B}, ya.options().dtype(at::kFloat));
-    tds_cross_entropy(logits.data_ptr<float>(), labels.data_ptr<int64_t>(), row_loss.data_ptr<float>(),
-                      dlogits.data_ptr<float>(), loss.data_ptr<float>(), inv.data_ptr<float>(), (int)B, (int)NC, -100,
-                      0.f, st);
-  }
-  check_launches("fused_head_forward_aff_ce");
-  return {logits, loss, dlogits};
+  const auto ws = head_fwd("fused_head_forward_aff_ce", ya, b2, mag, wfc, bfc, P, x_out, finished_aff(aff2), labels);
+  return {ws[WS_LOGITS], ws[WS_LOSS], ws[WS_DLOGITS]};
 }
 
 // The head forward in channel-range launches (the activation exchange's column groups, parallel/
@@ -644,14 +705,11 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> head_forward_range_ws
                                                                                  int64_t P) {
   TORCH_CHECK(ya.is_cuda() && ya.dim() == 3 && wfc.dim() == 2,
               "head_forward_range_ws: ya [B,32,PB] on the GPU, fc.weight [NC,K]");
-  const int64_t B = ya.size(0), Q = P / 2, NC = wfc.size(0);
   c10::DeviceGuard guard(ya.device());
   TORCH_CHECK(tds_head_fwd_range_begin(stream_of(ya)) == 0,
               "head_forward_range_ws: could not reset the head forward's counters");
-  const int nblk = 32 * tds_head_pb_nblk((int)Q);
-  auto o = ya.options().dtype(at::kFloat);
-  return {at::empty({(int64_t)(nblk + 32) * B * NC}, o.dtype(at::kDouble)), at::empty({B * NC}, o.dtype(at::kDouble)),
-          at::empty({B, NC}, o), at::empty({B, NC}, o), at::empty({}, o), at::empty({1}, o)};
+  const auto ws = head_ws(ya, HeadDims{ya.size(0), P / 2, wfc.size(0)}, WS_ALL);
+  return {ws[WS_PART], ws[WS_LSUM], ws[WS_LOGITS], ws[WS_DLOGITS], ws[WS_LOSS], ws[WS_INV]};
 }
 
 void fused_head_forward_range(const Tensor& ya, const Tensor& aff2, const Tensor& b2, const c10::optional<Tensor>& mag,
@@ -659,41 +717,8 @@ void fused_head_forward_range(const Tensor& ya, const Tensor& aff2, const Tensor
                               int64_t P, int64_t c0, int64_t c1, const Tensor& part, const Tensor& lsum,
                               const Tensor& logits, const Tensor& dlogits, const Tensor& loss, const Tensor& inv,
                               const c10::optional<Tensor>& labels, const c10::optional<Tensor>& x_out) {
-  TORCH_CHECK(ya.dim() == 3 && ya.size(1) == 32, "fused_head_forward_range: ya must be [B,32,PB]");
-  const int64_t B = ya.size(0), Q = P / 2;
-  TORCH_CHECK(Q >= 4 && B >= 1 && B <= 8, "fused_head_forward_range: needs P/2 >= 4 and 1 <= B <= 8 (one pass)");
-  TORCH_CHECK(0 <= c0 && c0 < c1 && c1 <= 32, "fused_head_forward_range: channels 0 <= c0 < c1 <= 32");
-  need(ya, at::kHalf, {B, 32, pb_plane(P)}, "ya (fp16)");
-  need(aff2, at::kFloat, {64}, "aff2");
-  TORCH_CHECK(wfc.dim() == 2 && wfc.size(1) == 32 * Q * Q && wfc.size(0) >= 1 && wfc.size(0) <= 10,
-              "fc.weight must be [<=10, 32*Q*Q]");
-  const int64_t NC = wfc.size(0);
-  need(wfc, at::kFloat, {NC, 32 * Q * Q}, "fc.weight");
-  const float* bf = optf(bfc, NC, "fc.bias");
-  const int nblk = 32 * tds_head_pb_nblk((int)Q);
-  need(part, at::kDouble, {(int64_t)(nblk + 32) * B * NC}, "head partials");
-  need(lsum, at::kDouble, {B * NC}, "logit sums");
-  need(logits, at::kFloat, {B, NC}, "logits");
-  need(dlogits, at::kFloat, {B, NC}, "dlogits");
-  need(loss, at::kFloat, {}, "loss");
-  need(inv, at::kFloat, {1}, "1/count");
-  const int64_t* lab = nullptr;
-  if (labels.has_value() && labels->defined()) {
-    need(*labels, at::kLong, {B}, "labels");
-    lab = labels->data_ptr<int64_t>();
-  }
-  float* xo = nullptr;
-  if (x_out.has_value() && x_out->defined()) {
-    need(*x_out, at::kFloat, {B, (c1 - c0) * Q * Q}, "x_out (the range's fc input rows)");
-    xo = x_out->data_ptr<float>();
-  }
-  c10::DeviceGuard guard(ya.device());
-  const int rc = tds_head_fwd_pb(ya_out(ya), ya_dec(b2, mag), wfc.data_ptr<float>(), bf, aff2.data_ptr<float>(),
-                                 part.data_ptr<double>(), lsum.data_ptr<double>(), logits.data_ptr<float>(), xo, (int)B,
-                                 (int)Q, (int)NC, stream_of(ya), true, lab, dlogits.data_ptr<float>(),
-                                 loss.data_ptr<float>(), inv.data_ptr<float>(), (int)c0, (int)c1);
-  TORCH_CHECK(rc >= 0, "fused_head_forward_range: unsupported shape or no in-launch finalize (TDS_FUSED_FIN=0)");
-  check_launches("fused_head_forward_range");
+  const std::vector<Tensor> ws{part, lsum, logits, dlogits, loss, inv};
+  head_fwd("fused_head_forward_range", ya, b2, mag, wfc, bfc, P, x_out, finished_aff(aff2), labels, &ws, c0, c1);
 }
 
 // The activation exchange's "pooled" source (parallel/factored.py): the ranks all-gather ya and a
@@ -714,36 +739,43 @@ Tensor head_pooled_record(const Tensor& aff2, const Tensor& b2, const c10::optio
   return rec;
 }
 
-void head_update_pooled(const Tensor& dl_all, const Tensor& ya_all, const Tensor& rec_all, const Tensor& wfc,
-                        const c10::optional<Tensor>& out, int64_t P, double scale, double lr, int64_t mode) {
-  TORCH_CHECK(ya_all.dim() == 4 && ya_all.size(2) == 32, "head_update_pooled: ya_all must be [W,B,32,PB]");
-  const int64_t Wr = ya_all.size(0), B = ya_all.size(1), Q = P / 2;
-  TORCH_CHECK(Q >= 4 && B >= 1 && B <= 8, "head_update_pooled: needs P/2 >= 4 and 1 <= B <= 8 images per rank");
-  TORCH_CHECK(mode >= 0 && mode <= 2, "head_update_pooled: mode 0 (update), 1 (=) or 2 (+=)");
-  need(ya_all, at::kHalf, {Wr, B, 32, pb_plane(P)}, "ya_all");
+// Both pooled updates: the columns of channels [c0, c1) from ya [W, B, c1-c0, PB], the ranks' planes
+// of those channels.  The full sweep (shard false) is [0, 32) by its own kernel.
+void head_update(const char* who, bool shard, const Tensor& dl_all, const Tensor& ya, const Tensor& rec_all,
+                 const Tensor& wfc, const c10::optional<Tensor>& out, int64_t P, int64_t c0, int64_t c1, double scale,
+                 double lr, int64_t mode) {
+  TORCH_CHECK(c0 >= 0 && c0 < c1 && c1 <= 32, who, ": needs 0 <= c0 < c1 <= 32");
+  const HeadDims d = head_dims(ya, wfc, P, who, true, c1 - c0, shard ? "ya_sh" : "ya_all");
+  const int64_t Wr = ya.size(0);
+  TORCH_CHECK(mode >= 0 && mode <= 2, who, ": mode 0 (update), 1 (=) or 2 (+=)");
   need(rec_all, at::kFloat, {Wr, 128}, "rec_all");
-  TORCH_CHECK(wfc.dim() == 2 && wfc.size(1) == 32 * Q * Q && wfc.size(0) >= 1 && wfc.size(0) <= 10,
-              "fc.weight must be [<=10, 32*Q*Q]");
-  const int64_t NC = wfc.size(0);
-  need(wfc, at::kFloat, {NC, 32 * Q * Q}, "fc.weight");
-  need(dl_all, at::kFloat, {Wr * B, NC}, "dl_all");
+  need(dl_all, at::kFloat, {Wr * d.B, d.NC}, "dl_all");
   float* o = wfc.data_ptr<float>();
   if (mode != 0) {
-    TORCH_CHECK(out.has_value() && out->defined(), "head_update_pooled: modes 1 and 2 write into out");
-    need(*out, at::kFloat, {NC, 32 * Q * Q}, "out (dW)");
+    TORCH_CHECK(out.has_value() && out->defined(), who, ": modes 1 and 2 write into out");
+    need(*out, at::kFloat, {d.NC, d.K()}, "out (dW)");
     o = out->data_ptr<float>();
   } else {
-    TORCH_CHECK(lr > 0.0, "head_update_pooled: mode 0 needs lr > 0");
+    TORCH_CHECK(lr > 0.0, who, ": mode 0 needs lr > 0");
   }
   // (the weight-layout stores pick their width from the row's alignment class: 16-B aligned bases)
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(o) % 16 == 0 && reinterpret_cast<uintptr_t>(wfc.data_ptr()) % 16 == 0,
-              "head_update_pooled: fc.weight and out must be 16-B aligned");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(o) % 16 == 0 && reinterpret_cast<uintptr_t>(wfc.data_ptr()) % 16 == 0, who,
+              ": fc.weight and out must be 16-B aligned");
   c10::DeviceGuard guard(wfc.device());
-  const int rc = tds_head_upd_pb(ya_out(ya_all), B * 32 * pb_plane(P), rec_all.data_ptr<float>(), (int)Wr,
-                                 dl_all.data_ptr<float>(), wfc.data_ptr<float>(), o, (int)B, (int)Q, (int)NC,
-                                 (float)scale, (float)lr, (int)mode, stream_of(wfc));
-  TORCH_CHECK(rc == 0, "head_update_pooled: unsupported shape");
-  check_launches("head_update_pooled");
+  const int rc =
+      shard ? tds_head_upd_pb_shard(ya_out(ya), rec_all.data_ptr<float>(), (int)Wr, dl_all.data_ptr<float>(),
+                                    wfc.data_ptr<float>(), o, (int)d.B, (int)d.Q, (int)d.NC, (int)c0, (int)c1,
+                                    (float)scale, (float)lr, (int)mode, stream_of(wfc))
+            : tds_head_upd_pb(ya_out(ya), d.B * 32 * pb_plane(P), rec_all.data_ptr<float>(), (int)Wr,
+                              dl_all.data_ptr<float>(), wfc.data_ptr<float>(), o, (int)d.B, (int)d.Q, (int)d.NC,
+                              (float)scale, (float)lr, (int)mode, stream_of(wfc));
+  TORCH_CHECK(rc == 0, who, ": unsupported shape");
+  check_launches(who);
+}
+
+void head_update_pooled(const Tensor& dl_all, const Tensor& ya_all, const Tensor& rec_all, const Tensor& wfc,
+                        const c10::optional<Tensor>& out, int64_t P, double scale, double lr, int64_t mode) {
+  head_update("head_update_pooled", false, dl_all, ya_all, rec_all, wfc, out, P, 0, 32, scale, lr, mode);
 }
 
 // The shard form (the sharded exchange's "pooled-sharded" source): this rank owns the fc columns of
@@ -753,137 +785,56 @@ void head_update_pooled(const Tensor& dl_all, const Tensor& ya_all, const Tensor
 void head_update_pooled_shard(const Tensor& dl_all, const Tensor& ya_sh, const Tensor& rec_all, const Tensor& wfc,
                               const c10::optional<Tensor>& out, int64_t P, int64_t c0, int64_t c1, double scale,
                               double lr, int64_t mode) {
-  TORCH_CHECK(c0 >= 0 && c0 < c1 && c1 <= 32, "head_update_pooled_shard: needs 0 <= c0 < c1 <= 32");
-  TORCH_CHECK(ya_sh.dim() == 4 && ya_sh.size(2) == c1 - c0, "head_update_pooled_shard: ya_sh must be [W,B,c1-c0,PB]");
-  const int64_t Wr = ya_sh.size(0), B = ya_sh.size(1), Q = P / 2;
-  TORCH_CHECK(Q >= 4 && B >= 1 && B <= 8, "head_update_pooled_shard: needs P/2 >= 4 and 1 <= B <= 8 images per rank");
-  TORCH_CHECK(mode >= 0 && mode <= 2, "head_update_pooled_shard: mode 0 (update), 1 (=) or 2 (+=)");
-  need(ya_sh, at::kHalf, {Wr, B, c1 - c0, pb_plane(P)}, "ya_sh");
-  need(rec_all, at::kFloat, {Wr, 128}, "rec_all");
-  TORCH_CHECK(wfc.dim() == 2 && wfc.size(1) == 32 * Q * Q && wfc.size(0) >= 1 && wfc.size(0) <= 10,
-              "fc.weight must be [<=10, 32*Q*Q]");
-  const int64_t NC = wfc.size(0);
-  need(wfc, at::kFloat, {NC, 32 * Q * Q}, "fc.weight");
-  need(dl_all, at::kFloat, {Wr * B, NC}, "dl_all");
-  float* o = wfc.data_ptr<float>();
-  if (mode != 0) {
-    TORCH_CHECK(out.has_value() && out->defined(), "head_update_pooled_shard: modes 1 and 2 write into out");
-    need(*out, at::kFloat, {NC, 32 * Q * Q}, "out (dW)");
-    o = out->data_ptr<float>();
-  } else {
-    TORCH_CHECK(lr > 0.0, "head_update_pooled_shard: mode 0 needs lr > 0");
-  }
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(o) % 16 == 0 && reinterpret_cast<uintptr_t>(wfc.data_ptr()) % 16 == 0,
-              "head_update_pooled_shard: fc.weight and out must be 16-B aligned");
-  c10::DeviceGuard guard(wfc.device());
-  const int rc = tds_head_upd_pb_shard(ya_out(ya_sh), rec_all.data_ptr<float>(), (int)Wr, dl_all.data_ptr<float>(),
-                                       wfc.data_ptr<float>(), o, (int)B, (int)Q, (int)NC, (int)c0, (int)c1,
-                                       (float)scale, (float)lr, (int)mode, stream_of(wfc));
-  TORCH_CHECK(rc == 0, "head_update_pooled_shard: unsupported shape");
-  check_launches("head_update_pooled_shard");
+  head_update("head_update_pooled_shard", true, dl_all, ya_sh, rec_all, wfc, out, P, c0, c1, scale, lr, mode);
 }
 
-// ---------------------------------------------------------------- head forward (BN2 finalize + fc)
-// returns (logits, stats2 [mean32|invstd32], aff2 [a32|b32])
-std::tuple<Tensor, Tensor, Tensor> fused_head_forward(
-    const Tensor& ya, const Tensor& partial2, const Tensor& b2, const c10::optional<Tensor>& gamma2,
-    const c10::optional<Tensor>& beta2, const c10::optional<Tensor>& rm2, const c10::optional<Tensor>& rv2,
-    const c10::optional<Tensor>& nbt2, double momentum, double eps, const Tensor& wfc, const c10::optional<Tensor>& bfc,
-    int64_t P, const c10::optional<Tensor>& x_out, const c10::optional<Tensor>& mag) {
-  TORCH_CHECK(ya.dim() == 3 && ya.size(1) == 32, "fused_head_forward: ya must be [B,32,PB]");
-  const int64_t B = ya.size(0), Q = P / 2;
-  TORCH_CHECK(Q >= 4 && B >= 1, "fused_head_forward: needs P/2 >= 4 pooled columns and B >= 1");
-  need(ya, at::kHalf, {B, 32, pb_plane(P)}, "ya (fp16)");
-  TORCH_CHECK(partial2.is_cuda() && partial2.scalar_type() == at::kDouble && partial2.numel() % 64 == 0, "partial2");
-  const int nch = (int)(partial2.numel() / 64);
-  need(b2, at::kFloat, {32}, "conv2.bias");
-  const float* g = optf(gamma2, 32, "bn2.weight");
-  const float* be = optf(beta2, 32, "bn2.bias");
-  float* rm = const_cast<float*>(optf(rm2, 32, "bn2.running_mean"));
-  float* rv = const_cast<float*>(optf(rv2, 32, "bn2.running_var"));
-  int64_t* nb = nullptr;
-  if (nbt2.has_value() && nbt2->defined()) {
-    TORCH_CHECK(nbt2->is_cuda() && nbt2->scalar_type() == at::kLong && nbt2->numel() == 1, "bn2.num_batches_tracked");
-    nb = nbt2->data_ptr<int64_t>();
-  }
-  TORCH_CHECK(wfc.dim() == 2 && wfc.size(1) == 32 * Q * Q && wfc.size(0) >= 1 && wfc.size(0) <= 10,
-              "fc.weight must be [<=10, 32*Q*Q]");
-  const int64_t NC = wfc.size(0);
-  need(wfc, at::kFloat, {NC, 32 * Q * Q}, "fc.weight");
-  const float* bf = optf(bfc, NC, "fc.bias");
-  float* xo = nullptr;
-  if (x_out.has_value() && x_out->defined()) {
-    need(*x_out, at::kFloat, {B, 32 * Q * Q}, "x_out (fc input rows)");
-    xo = x_out->data_ptr<float>();
-  }
-  c10::DeviceGuard guard(ya.device());
-  hipStream_t st = stream_of(ya);
-  auto stats = at::empty({64}, ya.options().dtype(at::kFloat));
-  auto aff = at::empty({64}, ya.options().dtype(at::kFloat));
-  tds_bn_reduce_finalize(partial2.data_ptr<double>(), 32, nch, B * P * P, b2.data_ptr<float>(), (float)eps,
-                         (float)momentum, g, be, stats.data_ptr<float>(), rm, rv, nb, aff.data_ptr<float>(), st);
-  const int nblk = 32 * tds_head_pb_nblk((int)Q);
-  auto part = at::empty({(int64_t)(nblk + 32) * B * NC}, ya.options().dtype(at::kDouble));
-  auto lsum = at::empty({B * NC}, ya.options().dtype(at::kDouble));
-  auto logits = at::empty({B, NC}, ya.options().dtype(at::kFloat));
-  const int rc = tds_head_fwd_pb(ya_out(ya), ya_dec(b2, mag), wfc.data_ptr<float>(), bf, aff.data_ptr<float>(),
-                                 part.data_ptr<double>(), lsum.data_ptr<double>(), logits.data_ptr<float>(), xo, (int)B,
-                                 (int)Q, (int)NC, st);
-  TORCH_CHECK(rc == 0, "fused_head_forward: unsupported shape");
-  check_launches("fused_head_forward");
-  return {logits, stats, aff};
-}
-
-// ---------------------------------------------------------------- head backward
-// fc / pool / ReLU / BN2 backward up to the pooled gradient g2m and the BN2 backward constants
-// kbuf = [k1|k2|k3] (dy2 = k1*dz + k2*y2 + k3, rebuilt tile by tile inside the conv2 backward).
-// update_lr > 0: the plain-SGD step of fc.weight runs in the same pass (W -= lr * dW).
-// returns (dW [into dw_out if given; empty when !compute_dw], db_fc, dgamma2, dbeta2, g2m, kbuf)
-// BN2 partial-sum workspace (doubles) of the head backward for B images at pooled size P/2
-// Host copy of the conv2 backward walk table (CPU int tensor [rows, nwg]) for tests/inspection.
-Tensor conv2_bwd_walk_table(int64_t B, int64_t tiles_r, int64_t tiles_c, int64_t nwg, int64_t seg) {
-  const int64_t n = tds_conv2_bwd_walk(nullptr, (int)B, (int)tiles_r, (int)tiles_c, (int)nwg, (int)seg);
-  TORCH_CHECK(n > 0, "conv2_bwd_walk_table: unsupported sizes");
-  auto t = at::empty({n / nwg, nwg}, at::TensorOptions().dtype(at::kInt));
-  tds_conv2_bwd_walk(t.data_ptr<int>(), (int)B, (int)tiles_r, (int)tiles_c, (int)nwg, (int)seg);
-  return t;
-}
-
-// The layer-1 kernels' tile walk (kernels/l1_tiles.h) of the workgroup whose first list entry is t0,
-// run on the host: the first n tiles as rows (b, tile row, tile col) of a CPU int tensor; rows past
-// the list have b >= B.  For tests.
-Tensor l1_tile_walk(int64_t t0, int64_t grid, int64_t tiles_r, int64_t tiles_c, int64_t n) {
-  TORCH_CHECK(t0 >= 0 && grid >= 1 && tiles_r >= 1 && tiles_c >= 1 && n >= 0, "l1_tile_walk: bad arguments");
-  auto t = at::empty({n, 3}, at::TensorOptions().dtype(at::kInt));
-  int* o = t.data_ptr<int>();
-  tds::L1Walk w = tds::l1_walk_begin((int)t0, (int)grid, (int)tiles_r, (int)tiles_c);
-  for (int64_t i = 0; i < n; ++i, tds::l1_walk_next(w, (int)tiles_r, (int)tiles_c)) {
-    o[3 * i] = w.b;
-    o[3 * i + 1] = w.tr;
-    o[3 * i + 2] = w.tc;
-  }
-  return t;
-}
-
-// Per-wave barrier-wait clocks of the last conv2 backward launch of a TDS_CONV2_DIAG=13 diag
-// build ([nwg][8][wait, total] shader-clock cycles; zeros in production builds).
-Tensor conv2_bwd_clock_dump(int64_t nwg) {
-  auto t = at::zeros({nwg, 8, 2}, at::TensorOptions().dtype(at::kInt));
-  const int n = tds_conv2_bwd_clock_read(reinterpret_cast<uint32_t*>(t.data_ptr<int>()), (int)(nwg * 16));
-  TORCH_CHECK(n >= 0, "conv2_bwd_clock_dump: hipMemcpyFromSymbol failed");
-  return t;
-}
-
-// the BN2 partials [32][npass * nblk][4] (fp32 dz / stored dz sums), then 16 doubles = g2m's 32 per-channel scales 2^-e_c (fp32)
-// for the K-chunked launches (the finalizing call copies them into kbuf[96..128))
+// BN2 partial-sum workspace (doubles) of the head backward for B images at pooled size P/2: the BN2
+// partials [32][npass * nblk][4] (fp32 dz / stored dz sums), then 16 doubles = g2m's 32 per-channel
+// scales 2^-e_c (fp32) for the K-chunked launches (the finalizing call copies them into kbuf[96..128))
 int64_t head_bwd_workspace(int64_t B, int64_t P) {
   const int Q = (int)(P / 2);
   return (int64_t)32 * tds_head_bwd_pb_npass((int)B) * tds_head_bwd_pb_nblk(Q) * 4 + 16;
 }
 
-// Channels [c_begin, c_end) of the head backward (K-chunked fc gradient): the caller passes the
-// same g2m_out / partial_out to every chunk and finalize=True on the last one, which then runs
-// the BN2 backward finalize and the bias gradient (outputs 1-3 and 5 are empty before that).
+// fused_head_backward's momentum arguments as the launcher's TdsHeadMom (head_pb.hip MOM: torch's SGD
+// with momentum / weight decay, the buffer updated in place beside the weight); none without mom_buf.
+// one_pass: the whole weight with its dW in one image pass; dw_kept: the caller's dW, if written.
+c10::optional<TdsHeadMom> head_mom(const c10::optional<Tensor>& mom_buf, double weight_decay, double momentum,
+                                   double dampening, bool nesterov, bool first_step, const Tensor& wfc, bool upd,
+                                   bool one_pass, const Tensor* dw_kept) {
+  const char* who = "fused_head_backward";
+  if (!mom_buf.has_value() || !mom_buf->defined()) {
+    TORCH_CHECK(weight_decay == 0.0 && momentum == 0.0 && dampening == 0.0 && !nesterov && !first_step, who,
+                ": weight_decay / momentum / dampening / nesterov / first_step need mom_buf");
+    return c10::nullopt;
+  }
+  TORCH_CHECK(upd, who, ": the momentum step needs update_lr > 0");
+  TORCH_CHECK(one_pass, who, ": the momentum step runs on the whole weight in one pass (<= 8 images)");
+  TORCH_CHECK(momentum > 0.0 && weight_decay >= 0.0, who, ": mom_buf needs momentum > 0, weight_decay >= 0");
+  TORCH_CHECK(!nesterov || dampening == 0.0, who, ": nesterov needs zero dampening");
+  need(*mom_buf, at::kFloat, wfc.sizes().vec(), "mom_buf");
+  TORCH_CHECK(mom_buf->device() == wfc.device(), who, ": mom_buf is on another device than fc.weight");
+  const char* m0 = static_cast<const char*>(mom_buf->data_ptr());
+  const int64_t nbytes = (int64_t)wfc.nbytes();
+  auto apart = [&](const Tensor& t) {
+    const char* t0 = static_cast<const char*>(t.data_ptr());
+    return m0 + nbytes <= t0 || t0 + nbytes <= m0;
+  };
+  TORCH_CHECK(apart(wfc), who, ": mom_buf aliases fc.weight");
+  TORCH_CHECK(dw_kept == nullptr || apart(*dw_kept), who, ": mom_buf aliases dw_out");
+  return TdsHeadMom{mom_buf->data_ptr<float>(), (float)weight_decay, (float)momentum, (float)dampening, nesterov,
+                    first_step};
+}
+
+// ---------------------------------------------------------------- head backward
+// fc / pool / ReLU / BN2 backward up to the pooled gradient g2m and the BN2 backward constants
+// kbuf = [k1|k2|k3] (dy2 = k1*dz + k2*y2 + k3, rebuilt tile by tile inside the conv2 backward).
+// update_lr > 0: the SGD step of fc.weight runs in the same pass (W -= lr * dW; with mom_buf, torch's
+// momentum / weight-decay rule).
+// returns (dW [into dw_out if given; empty when !compute_dw], db_fc, dgamma2, dbeta2, g2m, kbuf)
+// Channels [c_begin, c_end) only (K-chunked fc gradient): the caller passes the same g2m_out /
+// partial_out to every chunk and finalize=True on the last one, which then runs the BN2 backward
+// finalize and the bias gradient (outputs 1-3 and 5 are empty before that).
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fused_head_backward(
     const Tensor& dlogits, const Tensor& ya, const Tensor& stats2, const Tensor& aff2, const Tensor& b2,
     const c10::optional<Tensor>& gamma2, const Tensor& wfc, int64_t P, const c10::optional<Tensor>& dw_out,
@@ -892,135 +843,93 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fused_head_backward(
     int64_t c_end, bool finalize, const c10::optional<Tensor>& g2m_out, const c10::optional<Tensor>& partial_out,
     const c10::optional<Tensor>& mag, bool ypart_done, const c10::optional<Tensor>& mom_buf, double weight_decay,
     double momentum, double dampening, bool nesterov, bool first_step) {
-  TORCH_CHECK(ya.dim() == 3 && ya.size(1) == 32, "fused_head_backward: ya must be [B,32,PB]");
-  const int64_t B = ya.size(0), Q = P / 2;
-  TORCH_CHECK(Q >= 4 && B >= 1, "fused_head_backward: needs P/2 >= 4 pooled columns and B >= 1");
-  TORCH_CHECK(0 <= c_begin && c_begin < c_end && c_end <= 32, "fused_head_backward: bad channel range");
-  need(ya, at::kHalf, {B, 32, pb_plane(P)}, "ya (fp16)");
-  const int64_t NC = wfc.size(0);
-  need(wfc, at::kFloat, {NC, 32 * Q * Q}, "fc.weight");
+  const char* who = "fused_head_backward";
+  // 1. the arguments: everything is checked before anything is queued
+  const HeadDims d = head_dims(ya, wfc, P, who);
+  const int64_t B = d.B, Q = d.Q, NC = d.NC;
+  TORCH_CHECK(0 <= c_begin && c_begin < c_end && c_end <= 32, who, ": bad channel range");
   need(dlogits, at::kFloat, {B, NC}, "dlogits");
   need(stats2, at::kFloat, {64}, "stats2");
   need(aff2, at::kFloat, {64}, "aff2");
   const float* g = optf(gamma2, 32, "bn2.weight");
   const TdsYaDec yd = ya_dec(b2, mag);
+  const int nblk = tds_head_bwd_pb_nblk((int)Q), npass = tds_head_bwd_pb_npass((int)B);
+  const bool upd = update_lr > 0.0, whole = c_begin == 0 && c_end == 32;
+  auto given = [](const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); };
+  TORCH_CHECK(keep_dw || upd, who, ": keep_dw=False needs update_lr > 0 (update-only step)");
+  TORCH_CHECK(whole || !upd, who, ": the fused SGD step runs on the whole weight only");
+  TORCH_CHECK(!upd || (compute_dw && npass == 1), who, ": update_lr needs compute_dw and a batch of <= 8 images");
+  const c10::optional<TdsHeadMom> hm =
+      head_mom(mom_buf, weight_decay, momentum, dampening, nesterov, first_step, wfc, upd,
+               whole && compute_dw && npass == 1, keep_dw && given(dw_out) ? &*dw_out : nullptr);
+  // 2. outputs and workspaces: the caller's, or (a whole-weight call only) fresh ones
   c10::DeviceGuard guard(ya.device());
   hipStream_t st = stream_of(ya);
-  const bool upd = update_lr > 0.0;
-  TORCH_CHECK(keep_dw || upd, "fused_head_backward: keep_dw=False needs update_lr > 0 (update-only step)");
-  const bool whole = c_begin == 0 && c_end == 32;
-  TORCH_CHECK(whole || !upd, "fused_head_backward: the fused SGD step runs on the whole weight only");
-  // mom_buf: the fused step is torch's SGD with momentum / weight decay (head_pb.hip MOM), the
-  // buffer updated in place beside the weight; everything is checked before anything is launched
-  const bool mom = mom_buf.has_value() && mom_buf->defined();
-  TORCH_CHECK(mom || (weight_decay == 0.0 && momentum == 0.0 && dampening == 0.0 && !nesterov && !first_step),
-              "fused_head_backward: weight_decay / momentum / dampening / nesterov / first_step need mom_buf");
-  TdsHeadMom hm{};
-  if (mom) {
-    TORCH_CHECK(upd, "fused_head_backward: the momentum step needs update_lr > 0");
-    TORCH_CHECK(whole && compute_dw && tds_head_bwd_pb_npass((int)B) == 1,
-                "fused_head_backward: the momentum step runs on the whole weight in one pass (<= 8 images)");
-    TORCH_CHECK(momentum > 0.0 && weight_decay >= 0.0, "fused_head_backward: mom_buf needs momentum > 0, weight_decay >= 0");
-    TORCH_CHECK(!nesterov || dampening == 0.0, "fused_head_backward: nesterov needs zero dampening");
-    need(*mom_buf, at::kFloat, {NC, 32 * Q * Q}, "mom_buf");
-    TORCH_CHECK(mom_buf->device() == wfc.device(), "fused_head_backward: mom_buf is on another device than fc.weight");
-    const char* w0 = static_cast<const char*>(wfc.data_ptr());
-    const char* m0 = static_cast<const char*>(mom_buf->data_ptr());
-    const int64_t nbytes = NC * 32 * Q * Q * (int64_t)sizeof(float);
-    TORCH_CHECK(m0 + nbytes <= w0 || w0 + nbytes <= m0, "fused_head_backward: mom_buf aliases fc.weight");
-    if (dw_out.has_value() && dw_out->defined() && keep_dw) {
-      const char* d0 = static_cast<const char*>(dw_out->data_ptr());
-      TORCH_CHECK(m0 + nbytes <= d0 || d0 + nbytes <= m0, "fused_head_backward: mom_buf aliases dw_out");
+  auto callers = [&](const c10::optional<Tensor>& t, at::ScalarType dt, std::vector<int64_t> shape, const char* name) {
+    if (!given(t)) {
+      TORCH_CHECK(whole, who, ": a channel chunk writes into ", name);
+      return Tensor();
     }
-    hm = TdsHeadMom{mom_buf->data_ptr<float>(), (float)weight_decay, (float)momentum, (float)dampening, nesterov, first_step};
-  }
-  const TdsHeadMom* hmp = mom ? &hm : nullptr;
+    need(*t, dt, shape, name);
+    return *t;
+  };
   Tensor dW;  // undefined (None) for an update-only step
-  if (!compute_dw) {
-    dW = at::empty({0}, wfc.options());
-  } else if (!keep_dw) {
-  } else if (dw_out.has_value() && dw_out->defined()) {
-    need(*dw_out, at::kFloat, {NC, 32 * Q * Q}, "dW_out");
-    dW = *dw_out;
-  } else {
-    TORCH_CHECK(whole, "fused_head_backward: a channel chunk writes into dw_out");
-    dW = at::empty_like(wfc);
-  }
-  TORCH_CHECK(!upd || (compute_dw && tds_head_bwd_pb_npass((int)B) == 1),
-              "fused_head_backward: update_lr needs compute_dw and a batch of <= 8 images");
-  Tensor g2m;
-  if (g2m_out.has_value() && g2m_out->defined()) {
-    need(*g2m_out, at::kHalf, {B, 32, Q, Q}, "g2m_out");
-    g2m = *g2m_out;
-  } else {
-    TORCH_CHECK(whole, "fused_head_backward: a channel chunk writes into g2m_out");
-    // planar (the fc flatten order), with the 64 B of slack the conv2 backward's row loads may
-    // touch past the last row (conv2_bwd.hip BRStager GB)
-    g2m = at::empty({B * 32 * Q * Q + kG2mSlack}, ya.options().dtype(at::kHalf))
-              .narrow(0, 0, B * 32 * Q * Q)
+  if (!compute_dw) dW = at::empty({0}, wfc.options());
+  else if (keep_dw) dW = callers(dw_out, at::kFloat, {NC, d.K()}, "dw_out");
+  if (compute_dw && keep_dw && !dW.defined()) dW = at::empty_like(wfc);
+  // g2m: planar (the fc flatten order), with the 64 B of slack the conv2 backward's row loads may
+  // touch past the last row (conv2_bwd.hip BRStager GB)
+  Tensor g2m = callers(g2m_out, at::kHalf, {B, 32, Q, Q}, "g2m_out");
+  if (!g2m.defined())
+    g2m = at::empty({B * d.K() + kG2mSlack}, ya.options().dtype(at::kHalf)).narrow(0, 0, B * d.K())
               .view({B, 32, Q, Q});
-  }
-  const int nblk = tds_head_bwd_pb_nblk((int)Q), npass = tds_head_bwd_pb_npass((int)B);
-  Tensor partial;
-  if (partial_out.has_value() && partial_out->defined()) {
-    need(*partial_out, at::kDouble, {head_bwd_workspace(B, P)}, "partial_out");
-    partial = *partial_out;
-  } else {
-    TORCH_CHECK(whole, "fused_head_backward: a channel chunk writes into partial_out");
-    partial = at::empty({head_bwd_workspace(B, P)}, ya.options().dtype(at::kDouble));
-  }
+  Tensor partial = callers(partial_out, at::kDouble, {head_bwd_workspace(B, P)}, "partial_out");
+  if (!partial.defined()) partial = at::empty({head_bwd_workspace(B, P)}, ya.options().dtype(at::kDouble));
   // g2m's per-channel scales 2^-e_c: straight into kbuf[96..128) for a whole-weight call, into the
   // workspace tail for the channel chunks (copied at the finalizing call)
   auto kbuf = at::empty({128}, ya.options().dtype(at::kFloat));
-  float* g2inv_tail = reinterpret_cast<float*>(partial.data_ptr<double>() + (int64_t)32 * npass * nblk * 4);
-  float* g2inv = whole ? kbuf.data_ptr<float>() + 96 : g2inv_tail;
-  auto* g2p = reinterpret_cast<unsigned short*>(g2m.data_ptr<at::Half>());
-  uint32_t* gp = opt_mag(mag, mag_numel(B, P)) ? opt_mag(mag) + kMagParts + 32 * mag_ypart_count() : nullptr;
-  // the BN2 backward finalize inside the head backward's launch (head_pb.hip HBFin): one pass over
-  // all channels, with the conv2 forward having reduced its magnitude parts (ypart_done)
-  // (its one-round reducer takes at most 256 workgroups per channel: past that -- images beyond
-  // ~2048^2 pooled -- the separate finalize below)
+  const int64_t tail = (int64_t)32 * npass * nblk * 4;
+  float* g2inv = whole ? kbuf.data_ptr<float>() + 96 : reinterpret_cast<float*>(partial.data_ptr<double>() + tail);
+  uint32_t* m = opt_mag(mag, mag_numel(B, P));
+  uint32_t* gp = m ? m + kMagParts + 32 * mag_ypart_count() : nullptr;
+  Tensor dgamma, dbeta, dbfc;
+  if (finalize) {
+    dgamma = sink_or_empty(dg_out, {32}, ya, "dgamma2_out");
+    dbeta = sink_or_empty(dbe_out, {32}, ya, "dbeta2_out");
+    dbfc = sink_or_empty(dbfc_out, {NC}, ya, "dbfc_out");
+  }
+  // 3. the launch.  The BN2 backward finalize runs inside it (head_pb.hip HBFin) for one pass over all
+  // channels with the conv2 forward having reduced its magnitude parts (ypart_done); its one-round
+  // reducer takes at most 256 workgroups per channel: past that -- images beyond ~2048^2 pooled --
+  // the separate finalize below
   const bool fin_in = finalize && whole && npass == 1 && ypart_done && nblk <= 256 && tds_fused_fin_enabled();
+  Tensor cmax;
+  TdsHeadBwdFin hf{};
   if (fin_in) {
-    auto dgamma = sink_or_empty(dg_out, {32}, ya, "dgamma2_out");
-    auto dbeta = sink_or_empty(dbe_out, {32}, ya, "dbeta2_out");
-    auto dbfc = sink_or_empty(dbfc_out, {NC}, ya, "dbfc_out");
-    auto cmax = at::empty({32}, ya.options().dtype(at::kInt));
-    TdsHeadBwdFin hf{reinterpret_cast<uint32_t*>(cmax.data_ptr<int>()), stats2.data_ptr<float>(), g,
-                     dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), kbuf.data_ptr<float>(), dbfc.data_ptr<float>(),
-                     opt_mag(mag, mag_numel(B, P))};
-    const int rc = tds_head_bwd_pb(ya_out(ya), yd, wfc.data_ptr<float>(), aff2.data_ptr<float>(),
-                                   dlogits.data_ptr<float>(), g2p, partial.data_ptr<double>(),
-                                   compute_dw && dW.defined() ? dW.data_ptr<float>() : nullptr,
-                                   upd ? const_cast<float*>(wfc.data_ptr<float>()) : nullptr, (int)B, (int)Q, (int)NC,
-                                   (float)scale, (float)update_lr, 0, 32, gp, g2inv, st, &hf, hmp);
-    TORCH_CHECK(rc == 0, "fused_head_backward: unsupported shape (rc ", rc, ")");
-    check_launches("fused_head_backward");
-    return {dW, dbfc, dgamma, dbeta, g2m, kbuf};
+    cmax = at::empty({32}, ya.options().dtype(at::kInt));
+    hf = TdsHeadBwdFin{reinterpret_cast<uint32_t*>(cmax.data_ptr<int>()), stats2.data_ptr<float>(), g,
+                       dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), kbuf.data_ptr<float>(),
+                       dbfc.data_ptr<float>(), m};
   }
   const int rc = tds_head_bwd_pb(ya_out(ya), yd, wfc.data_ptr<float>(), aff2.data_ptr<float>(),
-                                 dlogits.data_ptr<float>(), g2p, partial.data_ptr<double>(),
-                                 compute_dw && dW.defined() ? dW.data_ptr<float>() : nullptr,
+                                 dlogits.data_ptr<float>(), reinterpret_cast<unsigned short*>(g2m.data_ptr<at::Half>()),
+                                 partial.data_ptr<double>(), compute_dw && dW.defined() ? dW.data_ptr<float>() : nullptr,
                                  upd ? const_cast<float*>(wfc.data_ptr<float>()) : nullptr, (int)B, (int)Q, (int)NC,
-                                 (float)scale, (float)update_lr, (int)c_begin, (int)c_end, gp, g2inv, st, nullptr, hmp);
-  TORCH_CHECK(rc == 0, "fused_head_backward: unsupported shape (rc ", rc, ")");
-  if (!finalize) {
-    check_launches("fused_head_backward");
-    const Tensor none = at::empty({0}, ya.options().dtype(at::kFloat));
-    return {dW, none, none, none, g2m, none};
+                                 (float)scale, (float)update_lr, (int)c_begin, (int)c_end, gp, g2inv, st,
+                                 fin_in ? &hf : nullptr, hm ? &*hm : nullptr);
+  TORCH_CHECK(rc == 0, who, ": unsupported shape (rc ", rc, ")");
+  // 4. the separate finalize, where the launch did not hold it
+  if (finalize && !fin_in) {
+    if (!whole) kbuf.narrow(0, 96, 32).copy_(partial.narrow(0, tail, 16).view(at::kFloat));
+    tds_bn_bwd_finalize2(partial.data_ptr<double>(), 32, npass * nblk, B * P * P, g, stats2.data_ptr<float>(),
+                         dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), kbuf.data_ptr<float>(), dlogits.data_ptr<float>(),
+                         (int)B, (int)NC, dbfc.data_ptr<float>(), (float)scale, m && !ypart_done ? m + kMagParts : nullptr,
+                         (int)mag_ypart_count(), gp, (int)mag_gpart_count(B, P), m, st);
   }
-  auto dgamma = sink_or_empty(dg_out, {32}, ya, "dgamma2_out");
-  auto dbeta = sink_or_empty(dbe_out, {32}, ya, "dbeta2_out");
-  if (!whole) kbuf.narrow(0, 96, 32).copy_(partial.narrow(0, (int64_t)32 * npass * nblk * 4, 16).view(at::kFloat));
-  auto dbfc = sink_or_empty(dbfc_out, {NC}, ya, "dbfc_out");
-  uint32_t* m = opt_mag(mag, mag_numel(B, P));
-  tds_bn_bwd_finalize2(partial.data_ptr<double>(), 32, npass * nblk, B * P * P, g, stats2.data_ptr<float>(),
-                       dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), kbuf.data_ptr<float>(), dlogits.data_ptr<float>(),
-                       (int)B, (int)NC, dbfc.data_ptr<float>(), (float)scale, m && !ypart_done ? m + kMagParts : nullptr,
-                       (int)mag_ypart_count(), m ? m + kMagParts + 32 * mag_ypart_count() : nullptr,
-                       (int)mag_gpart_count(B, P), m, st);
-  check_launches("fused_head_backward");
-  return {dW, dbfc, dgamma, dbeta, g2m, kbuf};
+  check_launches(who);
+  if (finalize) return {dW, dbfc, dgamma, dbeta, g2m, kbuf};
+  const Tensor none = at::empty({0}, ya.options().dtype(at::kFloat));
+  return {dW, none, none, none, g2m, none};
 }
 
 // ---------------------------------------------------------------- conv2 backward
@@ -1134,6 +1043,40 @@ void launch_probe(const Tensor& like, int64_t lds_bytes, int64_t threads) {
   c10::DeviceGuard guard(like.device());
   tds_launch_probe(nullptr, (int)lds_bytes, (int)threads, stream_of(like));
   check_launches("launch_probe");
+}
+
+// Host copy of the conv2 backward walk table (CPU int tensor [rows, nwg]) for tests/inspection.
+Tensor conv2_bwd_walk_table(int64_t B, int64_t tiles_r, int64_t tiles_c, int64_t nwg, int64_t seg) {
+  const int64_t n = tds_conv2_bwd_walk(nullptr, (int)B, (int)tiles_r, (int)tiles_c, (int)nwg, (int)seg);
+  TORCH_CHECK(n > 0, "conv2_bwd_walk_table: unsupported sizes");
+  auto t = at::empty({n / nwg, nwg}, at::TensorOptions().dtype(at::kInt));
+  tds_conv2_bwd_walk(t.data_ptr<int>(), (int)B, (int)tiles_r, (int)tiles_c, (int)nwg, (int)seg);
+  return t;
+}
+
+// The layer-1 kernels' tile walk (kernels/l1_tiles.h) of the workgroup whose first list entry is t0,
+// run on the host: the first n tiles as rows (b, tile row, tile col) of a CPU int tensor; rows past
+// the list have b >= B.  For tests.
+Tensor l1_tile_walk(int64_t t0, int64_t grid, int64_t tiles_r, int64_t tiles_c, int64_t n) {
+  TORCH_CHECK(t0 >= 0 && grid >= 1 && tiles_r >= 1 && tiles_c >= 1 && n >= 0, "l1_tile_walk: bad arguments");
+  auto t = at::empty({n, 3}, at::TensorOptions().dtype(at::kInt));
+  int* o = t.data_ptr<int>();
+  tds::L1Walk w = tds::l1_walk_begin((int)t0, (int)grid, (int)tiles_r, (int)tiles_c);
+  for (int64_t i = 0; i < n; ++i, tds::l1_walk_next(w, (int)tiles_r, (int)tiles_c)) {
+    o[3 * i] = w.b;
+    o[3 * i + 1] = w.tr;
+    o[3 * i + 2] = w.tc;
+  }
+  return t;
+}
+
+// Per-wave barrier-wait clocks of the last conv2 backward launch of a TDS_CONV2_DIAG=13 diag
+// build ([nwg][8][wait, total] shader-clock cycles; zeros in production builds).
+Tensor conv2_bwd_clock_dump(int64_t nwg) {
+  auto t = at::zeros({nwg, 8, 2}, at::TensorOptions().dtype(at::kInt));
+  const int n = tds_conv2_bwd_clock_read(reinterpret_cast<uint32_t*>(t.data_ptr<int>()), (int)(nwg * 16));
+  TORCH_CHECK(n >= 0, "conv2_bwd_clock_dump: hipMemcpyFromSymbol failed");
+  return t;
 }
 
 // ---------------------------------------------------------------- layer 1 backward

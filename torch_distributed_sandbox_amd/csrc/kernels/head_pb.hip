@@ -36,6 +36,8 @@
 // loads in flight while the current one is reduced) held 236 / 202 VGPRs in the forward / backward,
 // 2 waves per SIMD; one set holds 140 / 149, 3 waves, and measured 10 / 4 us faster in the step
 // (r6_s36, r6_s37).  64-bit indexing throughout (no buffer descriptors).
+#include <type_traits>
+
 #include "bf16x3.h"
 #include "common.h"
 #include "ce_small.h"
@@ -893,6 +895,19 @@ __global__ __launch_bounds__(HP_REC) void hp_record_kernel(const float* __restri
 
 using namespace tds;
 
+// A run-time choice as a template argument: f(std::integral_constant<int, i>{}) for i in [0, N)
+// (nothing outside: the launchers check their ranges first).  The kernels are templates over the
+// images of a pass (1 .. HP_MAXB) and their mode / flags; each launcher nests one pick per choice.
+template <int N, class F>
+static void hp_pick(int i, F&& f) {
+  if constexpr (N > 0) {
+    if (i == N - 1)
+      f(std::integral_constant<int, N - 1>{});
+    else
+      hp_pick<N - 1>(i, f);
+  }
+}
+
 void tds_head_pooled_record(const float* aff2, const float* b2, const uint32_t* ysc, float* rec, hipStream_t st) {
   hipLaunchKernelGGL(hp_record_kernel, dim3(1), dim3(HP_REC), 0, st, aff2, b2, ysc, rec);
   TDS_LAUNCH_CHECK();
@@ -903,25 +918,13 @@ int tds_head_upd_pb(const unsigned short* ya_all, int64_t ya_rs, const float* re
   if (B < 1 || B > HP_MAXB || NC < 1 || NC > 10 || Q < 4 || nranks < 1 || mode < 0 || mode > 2) return -1;
   const PBGeom g = pb_geom(Q);
   const int nwg = 32 * hp_grid_b(g).per_channel();
-#define TDS_HPU_M(NBV, MD)                                                                                        \
-  hipLaunchKernelGGL((head_upd_pb_kernel<NBV, MD>), dim3(nwg), dim3(HP_THREADS), 0, st, ya_all, ya_rs, rec, nranks, \
-                     dl, W, out, g, NC, scale, lr);
-#define TDS_HPU(NBV)                                    \
-  case NBV:                                             \
-    if (mode == 0) {                                    \
-      TDS_HPU_M(NBV, 0)                                 \
-    } else if (mode == 1) {                             \
-      TDS_HPU_M(NBV, 1)                                 \
-    } else {                                            \
-      TDS_HPU_M(NBV, 2)                                 \
-    }                                                   \
-    break;
-  switch (B) {
-    TDS_HPU(1) TDS_HPU(2) TDS_HPU(3) TDS_HPU(4) TDS_HPU(5) TDS_HPU(6) TDS_HPU(7) TDS_HPU(8)
-    default: return -1;
-  }
-#undef TDS_HPU
-#undef TDS_HPU_M
+  hp_pick<HP_MAXB>(B - 1, [&](auto nb) {
+    hp_pick<3>(mode, [&](auto md) {
+      constexpr int NB = decltype(nb)::value + 1, MODE = decltype(md)::value;
+      hipLaunchKernelGGL((head_upd_pb_kernel<NB, MODE>), dim3(nwg), dim3(HP_THREADS), 0, st, ya_all, ya_rs, rec, nranks,
+                         dl, W, out, g, NC, scale, lr);
+    });
+  });
   TDS_LAUNCH_CHECK();
   return 0;
 }
@@ -934,25 +937,13 @@ int tds_head_upd_pb_shard(const unsigned short* ya_sh, const float* rec, int nra
   const PBGeom g = pb_geom(Q);
   const int nc = c1 - c0;
   const int nwg = nc * g.Q4 * ((g.Q8 + 31) / 32);
-#define TDS_HPS_M(NBV, MD)                                                                                        \
-  hipLaunchKernelGGL((head_upd_pb_shard_kernel<NBV, MD>), dim3(nwg), dim3(HP_THREADS), 0, st, ya_sh, rec, nranks, \
-                     dl, W, out, g, NC, scale, lr, c0, nc);
-#define TDS_HPS(NBV)                                    \
-  case NBV:                                             \
-    if (mode == 0) {                                    \
-      TDS_HPS_M(NBV, 0)                                 \
-    } else if (mode == 1) {                             \
-      TDS_HPS_M(NBV, 1)                                 \
-    } else {                                            \
-      TDS_HPS_M(NBV, 2)                                 \
-    }                                                   \
-    break;
-  switch (B) {
-    TDS_HPS(1) TDS_HPS(2) TDS_HPS(3) TDS_HPS(4) TDS_HPS(5) TDS_HPS(6) TDS_HPS(7) TDS_HPS(8)
-    default: return -1;
-  }
-#undef TDS_HPS
-#undef TDS_HPS_M
+  hp_pick<HP_MAXB>(B - 1, [&](auto nb) {
+    hp_pick<3>(mode, [&](auto md) {
+      constexpr int NB = decltype(nb)::value + 1, MODE = decltype(md)::value;
+      hipLaunchKernelGGL((head_upd_pb_shard_kernel<NB, MODE>), dim3(nwg), dim3(HP_THREADS), 0, st, ya_sh, rec, nranks,
+                         dl, W, out, g, NC, scale, lr, c0, nc);
+    });
+  });
   TDS_LAUNCH_CHECK();
   return 0;
 }
@@ -1004,17 +995,11 @@ int tds_head_fwd_pb(const unsigned short* ya, TdsYaDec yd, const float* Wfc, con
   if (wmaxp == nullptr) return -2;
   for (int b0 = 0; b0 < B; b0 += HP_MAXB) {
     const int nb = B - b0 < HP_MAXB ? B - b0 : HP_MAXB;
-#define TDS_HPF(NBV)                                                                                                   \
-  case NBV:                                                                                                            \
-    hipLaunchKernelGGL((head_fwd_pb_kernel<NBV>), dim3(nwg), dim3(HP_THREADS), 0, st, ya, yd, Wfc, aff2, partial, xout, g, \
-                       B, b0, NC, fin, c0, x_rs, wmaxp);                                                               \
-    TDS_LAUNCH_CHECK();                                                                                                \
-    break;
-    switch (nb) {
-      TDS_HPF(1) TDS_HPF(2) TDS_HPF(3) TDS_HPF(4) TDS_HPF(5) TDS_HPF(6) TDS_HPF(7) TDS_HPF(8)
-      default: return -1;
-    }
-#undef TDS_HPF
+    hp_pick<HP_MAXB>(nb - 1, [&](auto nbi) {
+      hipLaunchKernelGGL((head_fwd_pb_kernel<decltype(nbi)::value + 1>), dim3(nwg), dim3(HP_THREADS), 0, st, ya, yd, Wfc,
+                         aff2, partial, xout, g, B, b0, NC, fin, c0, x_rs, wmaxp);
+    });
+    TDS_LAUNCH_CHECK();
   }
   if (fin.sync != nullptr) return labels != nullptr ? 1 : 0;
   hipLaunchKernelGGL(head_logits_kernel, dim3(BN), dim3(256), 0, st, partial, nwg, sums, bias, logits, BN, NC);
@@ -1035,6 +1020,17 @@ int tds_head_fwd_range_begin(hipStream_t st) {
 
 // partial: double [32][npass * nblk][2], npass = ceil(B / 8)
 int tds_head_bwd_pb_npass(int B) { return (B + HP_MAXB - 1) / HP_MAXB; }
+
+// The head_bwd_pb_kernel forms that are launched (its WITH_DW, ACC, UPD, KEEP, MOM), by what the call
+// asks for: 0 update only (dW formed, not stored), 1 no dW, 2 a later image pass (dW +=), 3 dW stored
+// and the weight stepped, 4 dW stored; with a momentum buffer 5 (dW stored too) and 6 (update only)
+struct HBForm {
+  bool with_dw, acc, upd, keep, mom;
+};
+constexpr HBForm HB_FORMS[7] = {{true, false, true, false, false}, {false, false, false, true, false},
+                                {true, true, false, true, false},  {true, false, true, true, false},
+                                {true, false, false, true, false}, {true, false, true, true, true},
+                                {true, false, true, false, true}};
 
 int tds_head_bwd_pb(const unsigned short* ya, TdsYaDec yd, const float* Wfc, const float* aff2, const float* dlogits, unsigned short* g2m,
                     double* partial, float* dW, float* Wupd, int B, int Q, int NC, float scale, float lr, int c0,
@@ -1067,58 +1063,26 @@ int tds_head_bwd_pb(const unsigned short* ya, TdsYaDec yd, const float* Wfc, con
     fin.mag = hf->mag;
   }
   const int nwg = (c1 - c0) * hp_grid_b(g).per_channel();
-  if (hm != nullptr) {
-    const SgdRule rule = SgdRule::make(lr, hm->wd, hm->momentum, hm->dampening, hm->nesterov ? 1 : 0, hm->first_step ? 1 : 0);
-#define TDS_HPM_E(NBV, KP)                                                                                             \
-  hipLaunchKernelGGL((head_bwd_pb_kernel<NBV, true, false, true, KP, true>), dim3(nwg), dim3(HP_THREADS), 0, st, ya, yd, \
-                     Wfc, aff2, dlogits, g2m, partial, dW, Wupd, g, 0, 0, 1, NC, scale, lr, 0, gpart, fin, wmaxp, wrows, B, \
-                     g2inv, hm->buf, rule);
-#define TDS_HPM(NBV)            \
-  case NBV:                     \
-    if (dW) {                   \
-      TDS_HPM_E(NBV, true)      \
-    } else {                    \
-      TDS_HPM_E(NBV, false)     \
-    }                           \
-    TDS_LAUNCH_CHECK();         \
-    break;
-    switch (B) {
-      TDS_HPM(1) TDS_HPM(2) TDS_HPM(3) TDS_HPM(4) TDS_HPM(5) TDS_HPM(6) TDS_HPM(7) TDS_HPM(8)
-      default: return -1;
-    }
-#undef TDS_HPM
-#undef TDS_HPM_E
-    return 0;
-  }
+  // (the momentum form is one pass over all channels, checked above: pass 0 of 1 from c0 = 0)
+  const SgdRule rule = hm == nullptr ? SgdRule{}
+                                     : SgdRule::make(lr, hm->wd, hm->momentum, hm->dampening, hm->nesterov ? 1 : 0,
+                                                     hm->first_step ? 1 : 0);
+  float* mbuf = hm != nullptr ? hm->buf : nullptr;
   for (int pass = 0; pass < npass; ++pass) {
     const int b0 = pass * HP_MAXB;
     const int nb = B - b0 < HP_MAXB ? B - b0 : HP_MAXB;
     const bool acc = pass > 0;
-#define TDS_HPB_E(NBV, WD, AC, UP, KP)                                                                             \
-  hipLaunchKernelGGL((head_bwd_pb_kernel<NBV, WD, AC, UP, KP>), dim3(nwg), dim3(HP_THREADS), 0, st, ya, yd, Wfc, aff2, \
-                     dlogits, g2m, partial, dW, Wupd, g, b0, pass, npass, NC, scale, lr, c0, gpart, fin, wmaxp, wrows, \
-                     B, g2inv, nullptr, SgdRule{});
-#define TDS_HPB(NBV)                                   \
-  case NBV:                                            \
-    if (!dW && Wupd) {                                 \
-      TDS_HPB_E(NBV, true, false, true, false)         \
-    } else if (!dW) {                                  \
-      TDS_HPB_E(NBV, false, false, false, true)        \
-    } else if (acc) {                                  \
-      TDS_HPB_E(NBV, true, true, false, true)          \
-    } else if (Wupd) {                                 \
-      TDS_HPB_E(NBV, true, false, true, true)          \
-    } else {                                           \
-      TDS_HPB_E(NBV, true, false, false, true)         \
-    }                                                  \
-    TDS_LAUNCH_CHECK();                                \
-    break;
-    switch (nb) {
-      TDS_HPB(1) TDS_HPB(2) TDS_HPB(3) TDS_HPB(4) TDS_HPB(5) TDS_HPB(6) TDS_HPB(7) TDS_HPB(8)
-      default: return -1;
-    }
-#undef TDS_HPB
-#undef TDS_HPB_E
+    const int form = hm != nullptr ? (dW ? 5 : 6) : !dW && Wupd ? 0 : !dW ? 1 : acc ? 2 : Wupd ? 3 : 4;
+    hp_pick<HP_MAXB>(nb - 1, [&](auto nbi) {
+      hp_pick<7>(form, [&](auto fi) {
+        constexpr int NB = decltype(nbi)::value + 1;
+        constexpr HBForm F = HB_FORMS[decltype(fi)::value];
+        hipLaunchKernelGGL((head_bwd_pb_kernel<NB, F.with_dw, F.acc, F.upd, F.keep, F.mom>), dim3(nwg), dim3(HP_THREADS),
+                           0, st, ya, yd, Wfc, aff2, dlogits, g2m, partial, dW, Wupd, g, b0, pass, npass, NC, scale, lr,
+                           c0, gpart, fin, wmaxp, wrows, B, g2inv, mbuf, rule);
+      });
+    });
+    TDS_LAUNCH_CHECK();
   }
   return 0;
 }

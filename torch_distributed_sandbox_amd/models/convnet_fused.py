@@ -345,27 +345,21 @@ class _Head(torch.autograd.Function):
         B, K = ya.shape[0], wfc.shape[1]
         upd, link.fc_update = link.fc_update, None
         pooled = link.pooled  # (its gathers were started right after the conv2 forward: forward below)
-        if pooled:
-            pass
-        elif link.bn_done and ex is not None and _FUSED_FIN and B <= 8 and ex.grouped(B, K):
-            logits = _head_forward_grouped(ops, ya, bn_b, b2, wfc, bfc, P, ex, upd, link)
-            ctx.save_for_backward(ya, bn_a, bn_b, b2, g2, wfc)
-            ctx.P = P
-            ctx.y2_meta = (y2.shape, y2.dtype, y2.device)
-            ctx.wfc_param = wfc
-            ctx.small = (bfc, g2, be2)
-            ctx.ex = ex
-            ctx.link = link
-            return logits
-        if upd is not None:
-            upd()  # the whole deferred update, before the weight is read
-        x_out = None
-        # the activation / sharded exchanges send the fc input rows X, which the head writes
-        if ex is not None and not pooled and ex.planned(B) in ("activations", "sharded"):
-            x_out = torch.empty((B, K), device=ya.device, dtype=torch.float32)
         if link.bn_done:  # (bn_a, bn_b) = BN2's (stats, affine), finalized by the conv2 forward
             stats2, aff2 = bn_a, bn_b
-            if link.labels is not None:
+        if not pooled and link.bn_done and ex is not None and _FUSED_FIN and B <= 8 and ex.grouped(B, K):
+            logits = _head_forward_grouped(ops, ya, aff2, b2, wfc, bfc, P, ex, upd, link)
+        else:
+            if upd is not None:
+                upd()  # the whole deferred update, before the weight is read
+            x_out = None
+            # the activation / sharded exchanges send the fc input rows X, which the head writes
+            if ex is not None and not pooled and ex.planned(B) in ("activations", "sharded"):
+                x_out = torch.empty((B, K), device=ya.device, dtype=torch.float32)
+            if not link.bn_done:  # bn_a = the conv2 forward's BN2 partials
+                logits, stats2, aff2 = ops.fused_head_forward(ya, bn_a, b2, g2, be2, rm2, rv2, nbt2, momentum, eps, wfc,
+                                                              bfc, P, x_out, mag=link.mag)
+            elif link.labels is not None:
                 # the loss and dlogits formed by the head forward's finalizing workgroup
                 logits, loss, dlogits = ops.fused_head_forward_aff_ce(ya, aff2, b2, link.mag, wfc, bfc, P, link.labels,
                                                                       x_out)
@@ -373,13 +367,10 @@ class _Head(torch.autograd.Function):
                 STATS["head_fused_ce"] += 1
             else:
                 logits = ops.fused_head_forward_aff(ya, aff2, b2, link.mag, wfc, bfc, P, x_out)
-        else:  # bn_a = the conv2 forward's BN2 partials
-            logits, stats2, aff2 = ops.fused_head_forward(ya, bn_a, b2, g2, be2, rm2, rv2, nbt2, momentum, eps, wfc,
-                                                          bfc, P, x_out, mag=link.mag)
-        if ex is not None and not pooled:
-            started = ex.begin(x_out, rows=B)
-            if not started:
-                raise RuntimeError("fc gradient exchange refused to start after ready() agreed")
+            if ex is not None and not pooled:
+                started = ex.begin(x_out, rows=B)
+                if not started:
+                    raise RuntimeError("fc gradient exchange refused to start after ready() agreed")
         ctx.save_for_backward(ya, stats2, aff2, b2, g2, wfc)
         ctx.P = P
         ctx.y2_meta = (y2.shape, y2.dtype, y2.device)
@@ -412,9 +403,10 @@ class _Head(torch.autograd.Function):
             chunks = ex.column_chunks(wfc.shape[1], planes=32)
             for i, (k0, k1) in enumerate(chunks):
                 last = i == len(chunks) - 1
-                res = ops.fused_head_backward(dlogits, ya, stats2, aff2, b2, g2, wfc, P, dst, 1.0, True, 0.0,
-                                              None, dg_o if last else None, dbe_o if last else None, True,
-                                              k0 // (Q * Q), k1 // (Q * Q), last, g2m_buf, part, ctx.link.mag)
+                res = ops.fused_head_backward(dlogits, ya, stats2, aff2, b2, g2, wfc, P, dw_out=dst, scale=1.0,
+                                              dg_out=dg_o if last else None, dbe_out=dbe_o if last else None,
+                                              c_begin=k0 // (Q * Q), c_end=k1 // (Q * Q), finalize=last,
+                                              g2m_out=g2m_buf, partial_out=part, mag=ctx.link.mag)
                 if acc_w:
                     dw[:, k0:k1].add_(dst[:, k0:k1])
                 ex.chunk_ready(dw, k0, k1)
@@ -425,33 +417,33 @@ class _Head(torch.autograd.Function):
             dW = dbfc = None
         elif ex is not None:
             # fc gradients come from the activation exchange (parallel/factored.py)
-            _, _, dg2, dbe2, g2m, kbuf = ops.fused_head_backward(dlogits, ya, stats2, aff2, b2, g2, wfc, P, None, 1.0,
-                                                                 False, mag=ctx.link.mag, ypart_done=ctx.link.bn_done)
+            _, _, dg2, dbe2, g2m, kbuf = ops.fused_head_backward(dlogits, ya, stats2, aff2, b2, g2, wfc, P, dw_out=None,
+                                                                 scale=1.0, compute_dw=False, mag=ctx.link.mag,
+                                                                 ypart_done=ctx.link.bn_done)
             ex.defer(dlogits)
             dW = dbfc = None
         else:
             # world size 1 under DDP(overlap_optimizer): the SGD step of the fc weight runs in
             # this same kernel (ops/fused_update.py)
-            lr, mom_args = None, ()
+            lr, mom = None, {}
             if ctx.needs_input_grad[12] and ya.shape[0] <= 8:  # one pass of head_bwd_pb_kernel
                 step = fused_update.take_step(ctx.wfc_param)
+                lr = step["lr"] if step is not None else fused_update.take(ctx.wfc_param)
                 if step is not None and step["buf"] is not None:
                     # momentum / weight decay: the kernel's momentum form steps the buffer in place too
-                    lr = step["lr"]
-                    mom_args = (step["buf"], step["weight_decay"], step["momentum"], step["dampening"],
-                                step["nesterov"], step["first_step"])
-                else:
-                    lr = step["lr"] if step is not None else fused_update.take(ctx.wfc_param)
+                    mom = {k: step[k] for k in ("weight_decay", "momentum", "dampening", "nesterov", "first_step")}
+                    mom["mom_buf"] = step["buf"]
             keep = not lr or fused_update.keep_grad(ctx.wfc_param)
             # the gradient's destination (DDP's bucket slot) only when a gradient is written: an
             # update-only step never requests the slot, so DDP never allocates it (ddp.py _lazy_from)
             dw_out = grad_sink.acquire(ctx.wfc_param if ctx.needs_input_grad[12] and keep else None, wfc.shape, wfc)
             dbfc_o, dg_o, dbe_o = _sinks(ctx, ctx.small, (13, 5, 6))
             dW, dbfc, dg2, dbe2, g2m, kbuf = ops.fused_head_backward(dlogits, ya, stats2, aff2, b2, g2, wfc, P,
-                                                                     dw_out if keep else None, 1.0, True,
-                                                                     float(lr or 0.0), dbfc_o, dg_o, dbe_o, keep,
-                                                                     0, 32, True, None, None, ctx.link.mag,
-                                                                     ctx.link.bn_done, *mom_args)
+                                                                     dw_out=dw_out if keep else None, scale=1.0,
+                                                                     update_lr=float(lr or 0.0), dbfc_out=dbfc_o,
+                                                                     dg_out=dg_o, dbe_out=dbe_o, keep_dw=keep,
+                                                                     mag=ctx.link.mag, ypart_done=ctx.link.bn_done,
+                                                                     **mom)
             if lr:
                 # update-only step: no gradient for the weight (dW is None), as in torch's
                 # optimizer-in-backward; the owner marks the parameter ready

@@ -138,61 +138,43 @@ class SGD(torch.optim.Optimizer):
         for group in self.param_groups:
             lr, mom, damp = group["lr"], group["momentum"], group["dampening"]
             wd, nest = group["weight_decay"], group["nesterov"]
-            if (self._flat is not None and mom == 0.0 and wd == 0.0 and self._flat_ok() and self._flat[0].is_cuda):
-                fp, fg = self._flat[0], self._flat_grad()
-                if self._deferred is None:
-                    _ext.ops().sgd_step_([fp], [fg], [], lr, 0.0, 0.0, 0.0, False, False)
-                    continue
-                ranges, runner = self._deferred
-                ps, gs, pos = [], [], 0
-                for off, n in ranges + [(fp.numel(), 0)]:
-                    if off > pos:
-                        ps.append(fp[pos:off])
-                        gs.append(fg[pos:off])
-                    pos = off + n
-                # small leftovers of the deferred ranges the owner wants stepped here, in this sweep
-                owner = getattr(runner, "__self__", None)
-                for off, n in (owner.take_inline_deferred() if hasattr(owner, "take_inline_deferred") else []):
-                    ps.append(fp[off:off + n])
-                    gs.append(fg[off:off + n])
-                if ps:
-                    _ext.ops().sgd_step_(ps, gs, [], lr, 0.0, 0.0, 0.0, False, False)
-                runner(lambda off, n, _lr=lr: _ext.ops().sgd_step_([fp[off:off + n]], [self._flat_grad()[off:off + n]],
-                                                                   [], _lr, 0.0, 0.0, 0.0, False, False))
-                continue
             if self._flat is not None and self._flat[0].is_cuda and self._flat_ok():
-                # momentum / weight decay on the flat buffers: the same sweeps with the rule's
-                # arguments and the flat momentum buffer's slices beside the parameter's
+                # one sweep over the flat buffers and, under DDP's overlap, the deferred ranges on its
+                # side stream.  With momentum the flat momentum buffer's slices go beside the
+                # parameter's; the plain step passes no buffers and a rule of zeros
+                plain = mom == 0.0 and wd == 0.0
                 fp, fg = self._flat[0], self._flat_grad()
                 fb = self._ensure_flat_mom() if mom != 0.0 else None
-                first = mom != 0.0 and self._mom_fresh
+                rule = (lr, 0.0, 0.0, 0.0, False, False) if plain else (lr, wd, mom, damp, nest,
+                                                                        mom != 0.0 and self._mom_fresh)
                 sl = (lambda off, n: [fb[off:off + n]]) if fb is not None else (lambda off, n: [])
 
-                def sweep(ps, gs, bs, _first=first):
-                    _ext.ops().sgd_step_(ps, gs, bs, lr, wd, mom, damp, nest, _first)
+                def sweep(ps, gs, bs, _rule=rule):
+                    _ext.ops().sgd_step_(ps, gs, bs, *_rule)
 
                 if self._deferred is None:
                     sweep([fp], [fg], [fb] if fb is not None else [])
+                else:
+                    ranges, runner = self._deferred
+                    ps, gs, bs, pos = [], [], [], 0
+                    for off, n in ranges + [(fp.numel(), 0)]:
+                        if off > pos:
+                            ps.append(fp[pos:off])
+                            gs.append(fg[pos:off])
+                            bs += sl(pos, off - pos)
+                        pos = off + n
+                    # small leftovers of the deferred ranges the owner wants stepped here, in this sweep
+                    owner = getattr(runner, "__self__", None)
+                    for off, n in (owner.take_inline_deferred() if hasattr(owner, "take_inline_deferred") else []):
+                        ps.append(fp[off:off + n])
+                        gs.append(fg[off:off + n])
+                        bs += sl(off, n)
+                    if ps:
+                        sweep(ps, gs, bs)
+                    # (always: the runner waits for the bucket's collective and fences the parameters)
+                    runner(lambda off, n: sweep([fp[off:off + n]], [self._flat_grad()[off:off + n]], sl(off, n)))
+                if not plain:  # (a plain step leaves a buffer created by a backward kernel's query fresh)
                     self._mom_fresh = False
-                    continue
-                ranges, runner = self._deferred
-                ps, gs, bs, pos = [], [], [], 0
-                for off, n in ranges + [(fp.numel(), 0)]:
-                    if off > pos:
-                        ps.append(fp[pos:off])
-                        gs.append(fg[pos:off])
-                        bs += sl(pos, off - pos)
-                    pos = off + n
-                owner = getattr(runner, "__self__", None)
-                for off, n in (owner.take_inline_deferred() if hasattr(owner, "take_inline_deferred") else []):
-                    ps.append(fp[off:off + n])
-                    gs.append(fg[off:off + n])
-                    bs += sl(off, n)
-                if ps:
-                    sweep(ps, gs, bs)
-                # (always: the runner waits for the bucket's collective and fences the parameters)
-                runner(lambda off, n: sweep([fp[off:off + n]], [self._flat_grad()[off:off + n]], sl(off, n)))
-                self._mom_fresh = False
                 continue
             params, grads, bufs, first = [], [], [], False
             for p in group["params"]:
