@@ -55,6 +55,28 @@ def test_walk_covers_every_tile_once_in_vertical_segments(B, tr, tc, nwg):
     assert max(lens) <= -(-total // nwg) + 2
 
 
+@pytest.mark.parametrize("B,tr,tc", [(255, 2, 1), (255, 5, 3), (200, 1, 1), (3, 40, 37)])
+def test_tile_order_covers_every_tile_once_with_an_unsigned_image_field(B, tr, tc):
+    """The conv2 forward's tile order (tds_tile_order_fill): b << 24 | tile_row << 12 | tile_col in an
+    int, so from b = 128 on the entry is negative and the image field must be read unsigned, as the
+    kernels do (conv2_fwd2.hip f2_tile); every (b, tile_row, tile_col) appears once."""
+    t = _ext.ops().conv2_tile_order_table(B, tr, tc)
+    assert t.dtype == torch.int32 and t.shape == (B * tr * tc,)
+    e = t.to(torch.int64) & 0xFFFFFFFF
+    b, r, c = e >> 24, (e >> 12) & 4095, e & 4095
+    assert int(b.max()) == B - 1 and int(r.max()) == tr - 1 and int(c.max()) == tc - 1
+    if B > 128:
+        assert bool((t[b >= 128] < 0).all())  # (the case is real: a signed shift would give b - 256)
+    seen = collections.Counter(zip(b.tolist(), r.tolist(), c.tolist()))
+    assert set(seen) == {(i, j, k) for i in range(B) for j in range(tr) for k in range(tc)}
+    assert max(seen.values()) == 1
+
+
+def test_tile_order_rejects_unsupported_sizes():
+    with pytest.raises(RuntimeError, match="unsupported"):
+        _ext.ops().conv2_tile_order_table(256, 1, 1)  # B > 255 (8-bit image field)
+
+
 def test_walk_rejects_unsupported_sizes():
     with pytest.raises(RuntimeError, match="unsupported"):
         _ext.ops().conv2_bwd_walk_table(64, 10, 10, 8, 24)  # B > 63 (6-bit image field)

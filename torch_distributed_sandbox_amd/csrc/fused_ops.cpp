@@ -1054,6 +1054,17 @@ Tensor conv2_bwd_walk_table(int64_t B, int64_t tiles_r, int64_t tiles_c, int64_t
   return t;
 }
 
+// Host copy of the conv2 forward's blocked tile order (tds_tile_order_fill, the row groups tile_order
+// launches with) as a CPU int tensor [B * tiles_r * tiles_c], for tests/inspection.
+Tensor conv2_tile_order_table(int64_t B, int64_t tiles_r, int64_t tiles_c) {
+  TORCH_CHECK(B >= 1 && B <= 255 && tiles_r >= 1 && tiles_r <= 4095 && tiles_c >= 1 && tiles_c <= 4095,
+              "conv2_tile_order_table: unsupported sizes");
+  auto t = at::empty({B * tiles_r * tiles_c}, at::TensorOptions().dtype(at::kInt));
+  const int rc = tds_tile_order_fill(t.data_ptr<int>(), (int)B, (int)tiles_r, (int)tiles_c, 16);
+  TORCH_CHECK(rc == 0, "conv2_tile_order_table: unsupported sizes");
+  return t;
+}
+
 // The layer-1 kernels' tile walk (kernels/l1_tiles.h) of the workgroup whose first list entry is t0,
 // run on the host: the first n tiles as rows (b, tile row, tile col) of a CPU int tensor; rows past
 // the list have b >= B.  For tests.
@@ -1333,6 +1344,7 @@ TORCH_LIBRARY_FRAGMENT(tdsa, m) {
   m.def("mag_ypart_count() -> int", &mag_ypart_count);
   m.def("conv2_bwd_clock_dump(int nwg) -> Tensor", &conv2_bwd_clock_dump);
   m.def("conv2_bwd_walk_table(int B, int tiles_r, int tiles_c, int nwg, int seg) -> Tensor", &conv2_bwd_walk_table);
+  m.def("conv2_tile_order_table(int B, int tiles_r, int tiles_c) -> Tensor", &conv2_tile_order_table);
   m.def("l1_tile_walk(int t0, int grid, int tiles_r, int tiles_c, int n) -> Tensor", &l1_tile_walk);
   m.def(
       "fused_conv2_backward_y2(Tensor y2, Tensor a2, Tensor g2m, Tensor aff2, Tensor kbuf, Tensor b2, Tensor(c!) mag, Tensor p1, "

@@ -94,7 +94,8 @@ __device__ __forceinline__ s16x4 ldtr(const void* p) {
 // ---------------------------------------------------------------------------- tile order
 // L2-blocked tile order for the persistent conv kernels (built on the host by
 // tds_tile_order_fill, conv2_pack.hip; device table from the torch caching allocator, one int
-// per work index: b << 24 | tile_row << 12 | tile_col).  xcd_remap hands each XCD a contiguous
+// per work index: b << 24 | tile_row << 12 | tile_col; the image field is the word's top byte, read
+// UNSIGNED: b <= 255, and from b = 128 on the int is negative).  xcd_remap hands each XCD a contiguous
 // run of 64 work indices per round (grid = 512 = 8 XCDs x 64 workgroups), and t -> t + grid is
 // the same workgroup's next tile.  A plain row-major order makes those 64 tiles a 1-D strip,
 // so the 2-pixel halo above/below each tile (a third of the staged rows) is fetched again a
@@ -106,7 +107,7 @@ __device__ __forceinline__ s16x4 ldtr(const void* p) {
 // runtime integer divisions on the scalar unit.
 __device__ __forceinline__ void tile_from_order(const int* __restrict__ order, int t, int& b, int& tr, int& tc) {
   const int v = order[t];
-  b = v >> 24;
+  b = (int)((uint32_t)v >> 24);
   tr = (v >> 12) & 4095;
   tc = v & 4095;
 }

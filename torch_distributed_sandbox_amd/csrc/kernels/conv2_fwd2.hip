@@ -70,7 +70,7 @@ struct F2Tile {
 
 __device__ __forceinline__ F2Tile f2_tile(int entry, int P) {  // entry: conv2_common.h tile order
   F2Tile x;
-  x.b = entry >> 24;
+  x.b = (int)((uint32_t)entry >> 24);  // (unsigned: images 128 .. 255 set the sign bit)
   x.r0 = ((entry >> 12) & 4095) * F2_TH;
   x.c0 = (entry & 4095) * F2_TC;
   x.full = x.r0 + F2_TH <= P && x.c0 + F2_TC <= P;

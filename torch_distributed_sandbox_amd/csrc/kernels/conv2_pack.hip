@@ -95,8 +95,8 @@ void tds_conv2_wgrad_reduce(const float* slab, int nwg, float* dw, float* db, fl
 }
 
 // Blocked tile order (conv2_common.h) into a host array of B * tiles_r * tiles_c ints:
-// b << 24 | tile_row << 12 | tile_col.  Bands of 32 tile columns, row groups of GR tile rows,
-// column groups of 4 (one XCD round of the forward's 512 workgroups = one 16 x 4 block).  The
+// b << 24 | tile_row << 12 | tile_col (the image field unsigned: bits 24-31).  Bands of 32 tile
+// columns, row groups of GR tile rows, column groups of 4 (one XCD round of the forward's 512 workgroups = one 16 x 4 block).  The
 // binding layer copies it to a device tensor from the torch caching allocator and caches it
 // per (shape, GR).
 int tds_tile_order_fill(int* out, int B, int tiles_r, int tiles_c, int GR) {
@@ -116,7 +116,8 @@ int tds_tile_order_fill(int* out, int B, int tiles_r, int tiles_c, int GR) {
     off -= cg * GC * hg;
     const int wc = std::min(GC, wj - cg * GC);
     const int r = off / wc;
-    out[t] = (b << 24) | ((gr * GR + r) << 12) | (band * BC + cg * GC + (off - r * wc));
+    const uint32_t tr = (uint32_t)(gr * GR + r), tc = (uint32_t)(band * BC + cg * GC + (off - r * wc));
+    out[t] = (int)(((uint32_t)b << 24) | (tr << 12) | tc);
   }
   return 0;
 }
