@@ -61,6 +61,10 @@ HIP_FILE_FLAGS = {
     "x_autocorr.hip": ["-fno-slp-vectorize"],
     "conv2_bwd.hip": ["-fno-slp-vectorize"],
     "conv2_fwd2.hip": ["-fno-slp-vectorize"],
+    # the wide head's epilogues read every MFMA tile back (as above); no packed fp32 VALU: its sums and
+    # SGD steps are scalar fp32 by contract (bitwise the same values in every weight form)
+    "head_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Xclang", "-target-feature", "-Xclang",
+                      "-packed-fp32-ops"],
 }
 # A/B builds: TDS_NOSLP_FILES=a.hip,b.hip adds -fno-slp-vectorize to those files as well
 for _f in filter(None, os.environ.get("TDS_NOSLP_FILES", "").split(",")):

@@ -932,6 +932,176 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fused_head_backward(
   return {dW, none, none, none, g2m, none};
 }
 
+// ---------------------------------------------------------------- wide head: 11 .. 64 classes, <= 16 images
+// (kernels/head_wide.hip: the fc products on fp32 MFMA).  Ops of their own beside the ten-class ones,
+// which keep refusing a weight of more than 10 rows.  The forward returns wmax, its max |W| per
+// workgroup and class, and the backward of the same step takes it (g2m's fp16 scale).
+HeadDims head_wide_dims(const Tensor& ya, const Tensor& wfc, int64_t P, const char* who) {
+  const int64_t Q = P / 2;
+  TORCH_CHECK(ya.dim() == 3 && ya.size(1) == 32, who, ": ya must be [B,32,PB]");
+  const int64_t B = ya.size(0);
+  TORCH_CHECK(Q >= 4 && B >= 1 && B <= 16, who, ": needs P/2 >= 4 pooled columns and 1 <= B <= 16 images");
+  need(ya, at::kHalf, {B, 32, pb_plane(P)}, "ya");
+  TORCH_CHECK(wfc.dim() == 2 && wfc.size(1) == 32 * Q * Q && wfc.size(0) >= 11 && wfc.size(0) <= 64, who,
+              ": fc.weight must be [11..64, 32*Q*Q]");
+  need(wfc, at::kFloat, {wfc.size(0), 32 * Q * Q}, "fc.weight");
+  TORCH_CHECK(wfc.device() == ya.device(), who, ": fc.weight is on another device than ya");
+  return {B, Q, wfc.size(0)};
+}
+
+struct WideFwd {
+  Tensor logits, wmax, loss, dlogits;  // (loss, dlogits: empty without labels)
+};
+template <class Aff>
+WideFwd head_wide_fwd(const char* who, const Tensor& ya, const Tensor& b2, const c10::optional<Tensor>& mag,
+                      const Tensor& wfc, const c10::optional<Tensor>& bfc, int64_t P, Aff&& aff2,
+                      const c10::optional<Tensor>& labels = {}) {
+  const HeadDims d = head_wide_dims(ya, wfc, P, who);
+  const float* bf = optf(bfc, d.NC, "fc.bias");
+  const TdsYaDec yd = ya_dec(b2, mag);
+  const int64_t* lab = nullptr;
+  if (labels.has_value() && labels->defined()) {
+    need(*labels, at::kLong, {d.B}, "labels");
+    TORCH_CHECK(labels->device() == ya.device(), who, ": labels must be on ya's device");
+    lab = labels->data_ptr<int64_t>();
+  }
+  c10::DeviceGuard guard(ya.device());
+  hipStream_t st = stream_of(ya);
+  const float* aff = aff2();
+  const int64_t rows = 32 * tds_head_wide_nblk((int)d.Q);
+  auto fo = ya.options().dtype(at::kFloat);
+  auto partial = at::empty({rows * d.B * d.NC}, fo.dtype(at::kDouble));
+  WideFwd r{at::empty({d.B, d.NC}, fo), at::empty({rows, 64}, fo.dtype(at::kInt)), at::empty({0}, fo),
+            at::empty({0}, fo)};
+  const int rc = tds_head_wide_fwd(ya_out(ya), yd, wfc.data_ptr<float>(), bf, aff, partial.data_ptr<double>(),
+                                   reinterpret_cast<uint32_t*>(r.wmax.data_ptr<int>()), r.logits.data_ptr<float>(),
+                                   (int)d.B, (int)d.Q, (int)d.NC, st);
+  TORCH_CHECK(rc == 0, who, ": unsupported shape");
+  if (lab) {  // torch's CrossEntropyLoss defaults, as head_fwd
+    r.loss = at::empty({}, fo);
+    r.dlogits = at::empty({d.B, d.NC}, fo);
+    auto row_loss = at::empty({d.B}, fo), inv = at::empty({1}, fo);
+    tds_cross_entropy(r.logits.data_ptr<float>(), lab, row_loss.data_ptr<float>(), r.dlogits.data_ptr<float>(),
+                      r.loss.data_ptr<float>(), inv.data_ptr<float>(), (int)d.B, (int)d.NC, -100, 0.f, st);
+  }
+  check_launches(who);
+  return r;
+}
+
+// on a finished BN2 affine (fused_conv2_forward_bn's, inference_constants'): returns (logits, wmax,
+// loss, dlogits)
+std::tuple<Tensor, Tensor, Tensor, Tensor> fused_head_wide_forward_aff(
+    const Tensor& ya, const Tensor& aff2, const Tensor& b2, const c10::optional<Tensor>& mag, const Tensor& wfc,
+    const c10::optional<Tensor>& bfc, int64_t P, const c10::optional<Tensor>& labels) {
+  const WideFwd r = head_wide_fwd("fused_head_wide_forward_aff", ya, b2, mag, wfc, bfc, P, finished_aff(aff2), labels);
+  return {r.logits, r.wmax, r.loss, r.dlogits};
+}
+
+// BN2 finalized here from the conv2 forward's partials (as fused_head_forward): returns (logits,
+// stats2, aff2, wmax)
+std::tuple<Tensor, Tensor, Tensor, Tensor> fused_head_wide_forward(
+    const Tensor& ya, const Tensor& partial2, const Tensor& b2, const c10::optional<Tensor>& gamma2,
+    const c10::optional<Tensor>& beta2, const c10::optional<Tensor>& rm2, const c10::optional<Tensor>& rv2,
+    const c10::optional<Tensor>& nbt2, double momentum, double eps, const Tensor& wfc, const c10::optional<Tensor>& bfc,
+    int64_t P, const c10::optional<Tensor>& mag) {
+  TORCH_CHECK(partial2.is_cuda() && partial2.scalar_type() == at::kDouble && partial2.numel() % 64 == 0, "partial2");
+  const int nch = (int)(partial2.numel() / 64);
+  const float* g = optf(gamma2, 32, "bn2.weight");
+  const float* be = optf(beta2, 32, "bn2.bias");
+  float* rm = const_cast<float*>(optf(rm2, 32, "bn2.running_mean"));
+  float* rv = const_cast<float*>(optf(rv2, 32, "bn2.running_var"));
+  int64_t* nb = nullptr;
+  if (nbt2.has_value() && nbt2->defined()) {
+    TORCH_CHECK(nbt2->is_cuda() && nbt2->scalar_type() == at::kLong && nbt2->numel() == 1, "bn2.num_batches_tracked");
+    nb = nbt2->data_ptr<int64_t>();
+  }
+  Tensor stats, aff;
+  const WideFwd r = head_wide_fwd("fused_head_wide_forward", ya, b2, mag, wfc, bfc, P, [&] {
+    stats = at::empty({64}, ya.options().dtype(at::kFloat));
+    aff = at::empty({64}, ya.options().dtype(at::kFloat));
+    tds_bn_reduce_finalize(partial2.data_ptr<double>(), 32, nch, ya.size(0) * P * P, b2.data_ptr<float>(), (float)eps,
+                           (float)momentum, g, be, stats.data_ptr<float>(), rm, rv, nb, aff.data_ptr<float>(),
+                           stream_of(ya));
+    return aff.data_ptr<float>();
+  });
+  return {r.logits, stats, aff, r.wmax};
+}
+
+// The backward, one launch over the whole weight.  dW is written (keep_dw) and / or fc.weight stepped
+// in place (update_lr > 0: W -= lr dW, or with mom_buf torch's momentum / weight-decay rule, the
+// buffer stepped too).  returns (dW [undefined for an update-only step], db_fc, dgamma2, dbeta2, g2m,
+// kbuf) as fused_head_backward.
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fused_head_wide_backward(
+    const Tensor& dlogits, const Tensor& ya, const Tensor& stats2, const Tensor& aff2, const Tensor& b2,
+    const c10::optional<Tensor>& gamma2, const Tensor& wfc, const Tensor& wmax, int64_t P,
+    const c10::optional<Tensor>& dw_out, double scale, double update_lr, const c10::optional<Tensor>& dbfc_out,
+    const c10::optional<Tensor>& dg_out, const c10::optional<Tensor>& dbe_out, bool keep_dw,
+    const c10::optional<Tensor>& mag, bool ypart_done, const c10::optional<Tensor>& mom_buf, double weight_decay,
+    double momentum, double dampening, bool nesterov, bool first_step) {
+  const char* who = "fused_head_wide_backward";
+  // 1. the arguments: everything is checked before anything is queued
+  const HeadDims d = head_wide_dims(ya, wfc, P, who);
+  const int64_t B = d.B, Q = d.Q, NC = d.NC;
+  need(dlogits, at::kFloat, {B, NC}, "dlogits");
+  need(stats2, at::kFloat, {64}, "stats2");
+  need(aff2, at::kFloat, {64}, "aff2");
+  need(wmax, at::kInt, {(int64_t)32 * tds_head_wide_nblk((int)Q), 64}, "wmax (the wide forward's)");
+  const float* g = optf(gamma2, 32, "bn2.weight");
+  const TdsYaDec yd = ya_dec(b2, mag);
+  const bool upd = update_lr > 0.0;
+  auto given = [](const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); };
+  TORCH_CHECK(keep_dw || upd, who, ": keep_dw=False needs update_lr > 0 (update-only step)");
+  Tensor dW;  // undefined (None) for an update-only step
+  if (keep_dw && given(dw_out)) {
+    need(*dw_out, at::kFloat, {NC, d.K()}, "dw_out");
+    dW = *dw_out;
+  }
+  const c10::optional<TdsHeadMom> hm = head_mom(mom_buf, weight_decay, momentum, dampening, nesterov, first_step, wfc,
+                                                upd, true, dW.defined() ? &dW : nullptr);
+  // (the weight-layout stores pick their width from the row's alignment class: 16-B aligned bases)
+  auto al16 = [](const Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; };
+  TORCH_CHECK(al16(wfc) && (!dW.defined() || al16(dW)) && (!hm || al16(*mom_buf)), who,
+              ": fc.weight, dw_out and mom_buf must be 16-B aligned");
+  // 2. outputs and workspaces
+  c10::DeviceGuard guard(ya.device());
+  hipStream_t st = stream_of(ya);
+  auto fo = ya.options().dtype(at::kFloat);
+  if (keep_dw && !dW.defined()) dW = at::empty_like(wfc);
+  Tensor g2m = at::empty({B * d.K() + kG2mSlack}, fo.dtype(at::kHalf)).narrow(0, 0, B * d.K()).view({B, 32, Q, Q});
+  const int nblk = tds_head_bwd_pb_nblk((int)Q);
+  auto partial = at::empty({(int64_t)32 * nblk * 4}, fo.dtype(at::kDouble));
+  auto kbuf = at::empty({128}, fo);
+  uint32_t* m = opt_mag(mag, mag_numel(B, P));
+  uint32_t* gp = m ? m + kMagParts + 32 * mag_ypart_count() : nullptr;
+  Tensor dgamma = sink_or_empty(dg_out, {32}, ya, "dgamma2_out"), dbeta = sink_or_empty(dbe_out, {32}, ya, "dbeta2_out"),
+         dbfc = sink_or_empty(dbfc_out, {NC}, ya, "dbfc_out");
+  // 3. the launch, the BN2 backward finalize inside it when the conv2 forward reduced its magnitude
+  // parts (ypart_done), by the separate launch otherwise -- as fused_head_backward
+  const bool fin_in = ypart_done && tds_fused_fin_enabled();
+  Tensor cmax;
+  TdsHeadBwdFin hf{};
+  if (fin_in) {
+    cmax = at::empty({32}, fo.dtype(at::kInt));
+    hf = TdsHeadBwdFin{reinterpret_cast<uint32_t*>(cmax.data_ptr<int>()), stats2.data_ptr<float>(), g,
+                       dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), kbuf.data_ptr<float>(),
+                       dbfc.data_ptr<float>(), m};
+  }
+  const int rc = tds_head_wide_bwd(ya_out(ya), yd, wfc.data_ptr<float>(), aff2.data_ptr<float>(),
+                                   dlogits.data_ptr<float>(), reinterpret_cast<const uint32_t*>(wmax.data_ptr<int>()),
+                                   reinterpret_cast<unsigned short*>(g2m.data_ptr<at::Half>()), kbuf.data_ptr<float>() + 96,
+                                   partial.data_ptr<double>(), gp, dW.defined() ? dW.data_ptr<float>() : nullptr,
+                                   upd ? const_cast<float*>(wfc.data_ptr<float>()) : nullptr, (int)B, (int)Q, (int)NC,
+                                   (float)scale, (float)update_lr, st, fin_in ? &hf : nullptr, hm ? &*hm : nullptr);
+  TORCH_CHECK(rc == 0, who, ": unsupported shape (rc ", rc, ")");
+  if (!fin_in)
+    tds_bn_bwd_finalize2(partial.data_ptr<double>(), 32, nblk, B * P * P, g, stats2.data_ptr<float>(),
+                         dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), kbuf.data_ptr<float>(),
+                         dlogits.data_ptr<float>(), (int)B, (int)NC, dbfc.data_ptr<float>(), (float)scale,
+                         m && !ypart_done ? m + kMagParts : nullptr, (int)mag_ypart_count(), gp, 32 * nblk, m, st);
+  check_launches(who);
+  return {dW, dbfc, dgamma, dbeta, g2m, kbuf};
+}
+
 // ---------------------------------------------------------------- conv2 backward
 // BN2/ReLU/pool backward fused into conv2 dgrad + wgrad: (y2h, a2, g2m, aff2, kbuf, b2, p1) -> (dp1h, dw2,
 // db2); dp1h's decode factor lands in mag[kMagScales + 4] (fused_l1_backward's dp1_dec)
@@ -1322,6 +1492,22 @@ TORCH_LIBRARY_FRAGMENT(tdsa, m) {
         "Tensor labels, "
         "Tensor(a!)? x_out=None) -> (Tensor, Tensor, Tensor)",
         &fused_head_forward_aff_ce);
+  m.def("fused_head_wide_forward_aff(Tensor ya, Tensor aff2, Tensor b2, Tensor? mag, Tensor wfc, Tensor? bfc, int P, "
+        "Tensor? labels=None) -> (Tensor, Tensor, Tensor, Tensor)",
+        &fused_head_wide_forward_aff);
+  m.def(
+      "fused_head_wide_forward(Tensor ya, Tensor partial2, Tensor b2, Tensor? gamma2, Tensor? beta2, Tensor(a!)? rm2, "
+      "Tensor(b!)? rv2, Tensor(c!)? nbt2, float momentum, float eps, Tensor wfc, Tensor? bfc, int P, "
+      "Tensor? mag=None) -> (Tensor, Tensor, Tensor, Tensor)",
+      &fused_head_wide_forward);
+  m.def(
+      "fused_head_wide_backward(Tensor dlogits, Tensor ya, Tensor stats2, Tensor aff2, Tensor b2, Tensor? gamma2, "
+      "Tensor(e!) wfc, Tensor wmax, int P, Tensor(a!)? dw_out, float scale, float update_lr=0.0, "
+      "Tensor(b!)? dbfc_out=None, Tensor(c!)? dg_out=None, Tensor(d!)? dbe_out=None, bool keep_dw=True, "
+      "Tensor(h!)? mag=None, bool ypart_done=False, Tensor(i!)? mom_buf=None, float weight_decay=0.0, "
+      "float momentum=0.0, float dampening=0.0, bool nesterov=False, bool first_step=False) "
+      "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
+      &fused_head_wide_backward);
   m.def("head_bwd_workspace(int B, int P) -> int", &head_bwd_workspace);
   m.def("head_forward_range_ws(Tensor ya, Tensor wfc, int P) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
         &head_forward_range_ws);

@@ -278,6 +278,20 @@ int tds_head_bwd_pb(const unsigned short* ya, TdsYaDec yd, const float* Wfc, con
                     int c1, uint32_t* gpart, float* g2inv, hipStream_t st, const TdsHeadBwdFin* hf = nullptr,
                     const TdsHeadMom* hm = nullptr);
 
+// ---- head_wide.hip (the fc head for 11 .. 64 classes, <= 16 images: fp32 MFMA; other shapes: -1)
+int tds_head_wide_nblk(int Q);  // the forward's workgroups per channel (its partial / wmax rows)
+// partial: [32 * nblk][B*NC] doubles; wmax: [32 * nblk][64] words, max |W| per workgroup and class
+// (float bits) for the backward's g2m scale; logits finished by a second small launch
+int tds_head_wide_fwd(const unsigned short* ya, TdsYaDec yd, const float* Wfc, const float* bias, const float* aff2,
+                      double* partial, uint32_t* wmax, float* logits, int B, int Q, int NC, hipStream_t st);
+// one pass over all channels on tds_head_bwd_pb's grid (tds_head_bwd_pb_nblk bands per channel):
+// partial [32][nblk][4], gpart [32][nblk], g2m / g2inv / hf / hm as there.  dW and / or Wupd (the
+// step in place); hm needs Wupd and lr > 0.
+int tds_head_wide_bwd(const unsigned short* ya, TdsYaDec yd, const float* Wfc, const float* aff2, const float* dlogits,
+                      const uint32_t* wmax, unsigned short* g2m, float* g2inv, double* partial, uint32_t* gpart,
+                      float* dW, float* Wupd, int B, int Q, int NC, float scale, float lr, hipStream_t st,
+                      const TdsHeadBwdFin* hf = nullptr, const TdsHeadMom* hm = nullptr);
+
 // ---- zs_exchange.hip (zero-suppressed fc-input rows, parallel/zs.py)
 int64_t tds_zs_npages(int64_t n);
 // meta [npages * 65] (offsets + mask words), counts [npages] scratch, vals [cap] (dropped past

@@ -82,7 +82,10 @@ def _supported_config(model, x) -> bool:
         if not bn.track_running_stats or bn.momentum is None or not bn.affine:
             return False
     c1, c2 = model.layer1[0], model.layer2[0]
-    if c1.bias is None or c2.bias is None or model.fc.out_features > 10 or model.fc.bias is None:
+    if c1.bias is None or c2.bias is None or model.fc.out_features > 64 or model.fc.bias is None:
+        return False
+    # 11 .. 64 classes: the wide head (csrc/kernels/head_wide.hip) holds the batch in one 16-row MFMA tile
+    if model.fc.out_features > 10 and B > 16:
         return False
     if any(p.dtype != torch.float32 or not p.is_cuda for p in model.parameters()):
         return False
@@ -181,7 +184,7 @@ def _sinks(ctx, params, first):
 _ZERO = {}
 # counters the tests read: forward passes that applied the exchange's weight update in the head kernel,
 # and layer-1 forwards that took x moments precomputed by the input pipeline
-STATS = {"precomputed_input_moments": 0, "head_fused_ce": 0, "head_range_launches": 0}
+STATS = {"precomputed_input_moments": 0, "head_fused_ce": 0, "head_range_launches": 0, "head_wide": 0}
 
 
 def _zero_scalar(device, dtype):
@@ -347,7 +350,22 @@ class _Head(torch.autograd.Function):
         pooled = link.pooled  # (its gathers were started right after the conv2 forward: forward below)
         if link.bn_done:  # (bn_a, bn_b) = BN2's (stats, affine), finalized by the conv2 forward
             stats2, aff2 = bn_a, bn_b
-        if not pooled and link.bn_done and ex is not None and _FUSED_FIN and B <= 8 and ex.grouped(B, K):
+        wmax = None
+        if wfc.shape[0] > 10:
+            # 11 .. 64 classes: the wide head's ops (fp32 MFMA, head_wide.hip); no fc exchange (forward below)
+            if upd is not None:
+                upd()
+            if not link.bn_done:
+                logits, stats2, aff2, wmax = ops.fused_head_wide_forward(ya, bn_a, b2, g2, be2, rm2, rv2, nbt2, momentum,
+                                                                         eps, wfc, bfc, P, link.mag)
+            else:
+                logits, wmax, loss, dlogits = ops.fused_head_wide_forward_aff(ya, aff2, b2, link.mag, wfc, bfc, P,
+                                                                              link.labels)
+                if link.labels is not None:
+                    link.ce = (link.labels, loss, dlogits)
+                    STATS["head_fused_ce"] += 1
+            STATS["head_wide"] += 1
+        elif not pooled and link.bn_done and ex is not None and _FUSED_FIN and B <= 8 and ex.grouped(B, K):
             logits = _head_forward_grouped(ops, ya, aff2, b2, wfc, bfc, P, ex, upd, link)
         else:
             if upd is not None:
@@ -372,6 +390,7 @@ class _Head(torch.autograd.Function):
                 if not started:
                     raise RuntimeError("fc gradient exchange refused to start after ready() agreed")
         ctx.save_for_backward(ya, stats2, aff2, b2, g2, wfc)
+        ctx.wmax = wmax  # the wide forward's max |W| per workgroup and class (its backward's g2m scale)
         ctx.P = P
         ctx.y2_meta = (y2.shape, y2.dtype, y2.device)
         ctx.wfc_param = wfc
@@ -426,7 +445,8 @@ class _Head(torch.autograd.Function):
             # world size 1 under DDP(overlap_optimizer): the SGD step of the fc weight runs in
             # this same kernel (ops/fused_update.py)
             lr, mom = None, {}
-            if ctx.needs_input_grad[12] and ya.shape[0] <= 8:  # one pass of head_bwd_pb_kernel
+            wide = ctx.wmax is not None
+            if ctx.needs_input_grad[12] and (wide or ya.shape[0] <= 8):  # one pass of head_bwd_pb_kernel
                 step = fused_update.take_step(ctx.wfc_param)
                 lr = step["lr"] if step is not None else fused_update.take(ctx.wfc_param)
                 if step is not None and step["buf"] is not None:
@@ -438,12 +458,15 @@ class _Head(torch.autograd.Function):
             # update-only step never requests the slot, so DDP never allocates it (ddp.py _lazy_from)
             dw_out = grad_sink.acquire(ctx.wfc_param if ctx.needs_input_grad[12] and keep else None, wfc.shape, wfc)
             dbfc_o, dg_o, dbe_o = _sinks(ctx, ctx.small, (13, 5, 6))
-            dW, dbfc, dg2, dbe2, g2m, kbuf = ops.fused_head_backward(dlogits, ya, stats2, aff2, b2, g2, wfc, P,
-                                                                     dw_out=dw_out if keep else None, scale=1.0,
-                                                                     update_lr=float(lr or 0.0), dbfc_out=dbfc_o,
-                                                                     dg_out=dg_o, dbe_out=dbe_o, keep_dw=keep,
-                                                                     mag=ctx.link.mag, ypart_done=ctx.link.bn_done,
-                                                                     **mom)
+            # (the wide op takes its forward's wmax after the weight, the rest as the ten-class op)
+            head_bwd, w_args = ops.fused_head_backward, (wfc,)
+            if wide:
+                head_bwd, w_args = ops.fused_head_wide_backward, (wfc, ctx.wmax)
+            dW, dbfc, dg2, dbe2, g2m, kbuf = head_bwd(dlogits, ya, stats2, aff2, b2, g2, *w_args, P,
+                                                      dw_out=dw_out if keep else None, scale=1.0,
+                                                      update_lr=float(lr or 0.0), dbfc_out=dbfc_o, dg_out=dg_o,
+                                                      dbe_out=dbe_o, keep_dw=keep, mag=ctx.link.mag,
+                                                      ypart_done=ctx.link.bn_done, **mom)
             if lr:
                 # update-only step: no gradient for the weight (dW is None), as in torch's
                 # optimizer-in-backward; the owner marks the parameter ready
@@ -496,6 +519,10 @@ def forward(model, x):
     # agrees for the sharded path under source "pooled-sharded": ya's channel planes go to their
     # owners from here, and the head forward allocates no x_out and calls no ex.begin
     ex = factored.get(fc.weight)
+    if fc.out_features > 10:
+        # no fc exchange above ten classes (the wide head writes dW into the bucket): declined per
+        # step like a ready() that says no -- an exchange only claims the gradient once begun
+        ex = None
     B = x.shape[0]
     if ex is not None and link.bn_done and B <= 8 and ex.ready(B) and ex.pooled(B):
         ops = _ext.ops()
@@ -558,5 +585,7 @@ def forward_inference(model, x):
     param_fence.wait(fc.bias)
     if upd is not None:
         upd()  # the whole deferred update, before the weight is read
+    if fc.out_features > 10:
+        return ops.fused_head_wide_forward_aff(ya, aff2, conv2.bias, mag, fc.weight, fc.bias, p1.shape[1])[0]
     return ops.fused_head_forward_aff(ya, aff2, conv2.bias, mag, fc.weight, fc.bias, p1.shape[1], None)
 

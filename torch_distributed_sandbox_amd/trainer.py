@@ -46,6 +46,8 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--max-steps", default=0, type=int, help="stop after this many steps per epoch (0 = full epoch)")
     p.add_argument("--dataset-size", default=60000, type=int, help="synthetic MNIST size (reference: 60000)")
     p.add_argument("--log-interval", default=100, type=int)
+    p.add_argument("--num-classes", default=10, type=int,
+                   help="classes of the model and the synthetic data (the fused plan takes up to 64)")
     p.add_argument("--mode", default="auto", choices=["auto", "fused", "layers"], help="ConvNet execution plan")
     p.add_argument("--input", default="levels", choices=["levels", "fp32"],
                    help="batches as the resized images' uint8 levels (ToTensor's 1/255 folded into conv1) or as "
@@ -188,7 +190,7 @@ def train(gpu: int, args, distributed: bool = False) -> dict:
     device = _device(args, gpu)
     torch.manual_seed(0)
     H = W = args.image_size
-    model = ConvNet(image_shape=(H, W), device=device, mode=args.mode)
+    model = ConvNet(num_classes=args.num_classes, image_shape=(H, W), device=device, mode=args.mode)
     batch_size = args.batch_size
     criterion = CrossEntropyLoss()
     opt_args = {"momentum": float(getattr(args, "momentum", 0.0)), "weight_decay": float(getattr(args, "weight_decay", 0.0)),
@@ -210,7 +212,7 @@ def train(gpu: int, args, distributed: bool = False) -> dict:
     start_epoch = 0
     if args.resume:
         _, start_epoch, _ = checkpoint.load(args.resume, model, optimizer, map_location=device)
-    dataset = SyntheticMNIST(size=args.dataset_size)
+    dataset = SyntheticMNIST(size=args.dataset_size, num_classes=args.num_classes)
     levels = getattr(args, "input", "levels") == "levels"
     fused_plan = getattr(args, "mode", "auto") != "layers"
     moments = levels and fused_plan  # the fused plan reads them
@@ -292,7 +294,7 @@ def train(gpu: int, args, distributed: bool = False) -> dict:
     took = datetime.now() - start
     ev = None
     if getattr(args, "eval_size", 0) > 0:
-        test = SyntheticMNIST(size=args.eval_size, split="test")
+        test = SyntheticMNIST(size=args.eval_size, num_classes=args.num_classes, split="test")
         tsampler = DistributedSampler(len(test), num_replicas=world, rank=rank, shuffle=False) if distributed else None
         tloader = DeviceUpsampleLoader(test, getattr(args, "eval_batch_size", None) or batch_size, (H, W), device,
                                        sampler=tsampler, levels=levels)
