@@ -6,7 +6,9 @@ the weight and ya read, the weight (update-only step) and g2m written -- then th
 at ``--image-size``, batch ``--batch-size``, on the fused plan against ``mode="layers"`` (what a model
 of more than ten classes ran before the wide head), alternating ``--repeats`` times in one process.
 ``--ten`` adds the ten-class head's forward on the same box (the yardstick of the stream rate).
-Prints one JSON line.
+``--update`` adds the pooled exchange's fc step alone (``ops.head_update_pooled``, mode 0: the weight
+read and written, every rank's ya read) from one and from two ranks' inputs, the second rank's ya a copy
+of the first's.  Prints one JSON line.
 
     python tools/head_wide_bench.py --classes 26 62
 """
@@ -62,6 +64,22 @@ def _head_alone(ops, dev, H, B, NC, iters):
     return t_f, t_b, fwd_bytes, bwd_bytes
 
 
+def _update_alone(ops, dev, H, B, NC, W, iters):
+    """(ms, bytes) of the pooled exchange's update-only fc step from W ranks' pooled inputs."""
+    import torch
+
+    P, Q = H // 2, H // 4
+    K = 32 * Q * Q
+    plane = ((Q + 3) // 4) * ((Q + 7) // 8) * 32
+    ya_all = torch.randn(1, B, 32, plane, device=dev).half().repeat(W, 1, 1, 1)
+    wfc = torch.randn(NC, K, device=dev) * 0.01
+    aff2 = torch.cat([torch.ones(32, device=dev), torch.zeros(32, device=dev)])
+    rec_all = ops.head_pooled_record(aff2, torch.zeros(32, device=dev), None).repeat(W, 1)
+    dl = torch.randn(W * B, NC, device=dev) * 1e-3
+    t = _timed(lambda: ops.head_update_pooled(dl, ya_all, rec_all, wfc, None, P, 1.0 / W, 1e-6, 0), iters)
+    return t, 2 * 4 * NC * K + 2 * W * B * K
+
+
 def _stepper(dev, H, B, NC, mode, lr):
     import torch
 
@@ -97,6 +115,7 @@ def main(argv=None):
     ap.add_argument("--repeats", type=int, default=3, help="alternations fused / layers")
     ap.add_argument("--ten", action="store_true", help="also time the ten-class head alone")
     ap.add_argument("--no-step", action="store_true", help="the head alone only")
+    ap.add_argument("--update", action="store_true", help="also time the pooled exchange's fc step (W = 1, 2)")
     a = ap.parse_args(argv)
     import torch
 
@@ -113,6 +132,10 @@ def main(argv=None):
         t_f, t_b, by_f, by_b = _head_alone(ops, dev, H, B, NC, a.iters)
         r = {"head_fwd_ms": t_f, "head_fwd_tb_per_s": by_f / t_f / 1e9, "head_bwd_update_only_ms": t_b,
              "head_bwd_tb_per_s": by_b / t_b / 1e9}
+        if a.update:
+            for W in (1, 2):
+                t_u, by_u = _update_alone(ops, dev, H, B, NC, W, a.iters)
+                r[f"update_pooled_w{W}_ms"], r[f"update_pooled_w{W}_tb_per_s"] = t_u, by_u / t_u / 1e9
         torch.cuda.empty_cache()
         if NC > 10 and not a.no_step:
             fused, layers = [], []

@@ -739,13 +739,31 @@ Tensor head_pooled_record(const Tensor& aff2, const Tensor& b2, const c10::optio
   return rec;
 }
 
+// the full sweep's arguments for a weight of 11 .. 64 rows (kernels/head_wide.hip head_wide_upd_kernel):
+// up to 16 images per rank
+HeadDims head_wide_upd_dims(const Tensor& ya_all, const Tensor& wfc, int64_t P, const char* who) {
+  const int64_t Q = P / 2;
+  TORCH_CHECK(ya_all.dim() == 4 && ya_all.size(2) == 32, who, ": ya_all must be [W,B,32,PB]");
+  const int64_t B = ya_all.size(1);
+  TORCH_CHECK(Q >= 4 && ya_all.size(0) >= 1 && B >= 1 && B <= 16, who,
+              ": needs P/2 >= 4 pooled columns and 1 <= B <= 16 images per rank (11 .. 64 classes)");
+  need(ya_all, at::kHalf, {ya_all.size(0), B, 32, pb_plane(P)}, "ya_all");
+  TORCH_CHECK(wfc.size(1) == 32 * Q * Q && wfc.size(0) <= 64, who, ": fc.weight must be [<=64, 32*Q*Q]");
+  need(wfc, at::kFloat, {wfc.size(0), 32 * Q * Q}, "fc.weight");
+  TORCH_CHECK(wfc.device() == ya_all.device(), who, ": fc.weight is on another device than ya_all");
+  return {B, Q, wfc.size(0)};
+}
+
 // Both pooled updates: the columns of channels [c0, c1) from ya [W, B, c1-c0, PB], the ranks' planes
-// of those channels.  The full sweep (shard false) is [0, 32) by its own kernel.
+// of those channels.  The full sweep (shard false) is [0, 32) by its own kernel -- for more than ten
+// classes the wide head's (the shard form stays at ten).
 void head_update(const char* who, bool shard, const Tensor& dl_all, const Tensor& ya, const Tensor& rec_all,
                  const Tensor& wfc, const c10::optional<Tensor>& out, int64_t P, int64_t c0, int64_t c1, double scale,
                  double lr, int64_t mode) {
   TORCH_CHECK(c0 >= 0 && c0 < c1 && c1 <= 32, who, ": needs 0 <= c0 < c1 <= 32");
-  const HeadDims d = head_dims(ya, wfc, P, who, true, c1 - c0, shard ? "ya_sh" : "ya_all");
+  const bool wide = !shard && wfc.dim() == 2 && wfc.size(0) > 10;
+  const HeadDims d = wide ? head_wide_upd_dims(ya, wfc, P, who)
+                          : head_dims(ya, wfc, P, who, true, c1 - c0, shard ? "ya_sh" : "ya_all");
   const int64_t Wr = ya.size(0);
   TORCH_CHECK(mode >= 0 && mode <= 2, who, ": mode 0 (update), 1 (=) or 2 (+=)");
   need(rec_all, at::kFloat, {Wr, 128}, "rec_all");
@@ -763,7 +781,10 @@ void head_update(const char* who, bool shard, const Tensor& dl_all, const Tensor
               ": fc.weight and out must be 16-B aligned");
   c10::DeviceGuard guard(wfc.device());
   const int rc =
-      shard ? tds_head_upd_pb_shard(ya_out(ya), rec_all.data_ptr<float>(), (int)Wr, dl_all.data_ptr<float>(),
+      wide  ? tds_head_wide_upd(ya_out(ya), rec_all.data_ptr<float>(), (int)Wr, dl_all.data_ptr<float>(),
+                                wfc.data_ptr<float>(), o, (int)d.B, (int)d.Q, (int)d.NC, (float)scale, (float)lr,
+                                (int)mode, stream_of(wfc))
+      : shard ? tds_head_upd_pb_shard(ya_out(ya), rec_all.data_ptr<float>(), (int)Wr, dl_all.data_ptr<float>(),
                                     wfc.data_ptr<float>(), o, (int)d.B, (int)d.Q, (int)d.NC, (int)c0, (int)c1,
                                     (float)scale, (float)lr, (int)mode, stream_of(wfc))
             : tds_head_upd_pb(ya_out(ya), d.B * 32 * pb_plane(P), rec_all.data_ptr<float>(), (int)Wr,
@@ -1029,7 +1050,9 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> fused_head_wide_forward(
 
 // The backward, one launch over the whole weight.  dW is written (keep_dw) and / or fc.weight stepped
 // in place (update_lr > 0: W -= lr dW, or with mom_buf torch's momentum / weight-decay rule, the
-// buffer stepped too).  returns (dW [undefined for an update-only step], db_fc, dgamma2, dbeta2, g2m,
+// buffer stepped too).  compute_dw=False: the no-dW form of the activation exchange -- no dW product
+// and no weight store in the kernel, dW returned empty, every other output bitwise the dW form's.
+// returns (dW [undefined for an update-only step], db_fc, dgamma2, dbeta2, g2m,
 // kbuf) as fused_head_backward.
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fused_head_wide_backward(
     const Tensor& dlogits, const Tensor& ya, const Tensor& stats2, const Tensor& aff2, const Tensor& b2,
@@ -1037,7 +1060,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fused_head_wide_backw
     const c10::optional<Tensor>& dw_out, double scale, double update_lr, const c10::optional<Tensor>& dbfc_out,
     const c10::optional<Tensor>& dg_out, const c10::optional<Tensor>& dbe_out, bool keep_dw,
     const c10::optional<Tensor>& mag, bool ypart_done, const c10::optional<Tensor>& mom_buf, double weight_decay,
-    double momentum, double dampening, bool nesterov, bool first_step) {
+    double momentum, double dampening, bool nesterov, bool first_step, bool compute_dw) {
   const char* who = "fused_head_wide_backward";
   // 1. the arguments: everything is checked before anything is queued
   const HeadDims d = head_wide_dims(ya, wfc, P, who);
@@ -1051,6 +1074,9 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fused_head_wide_backw
   const bool upd = update_lr > 0.0;
   auto given = [](const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); };
   TORCH_CHECK(keep_dw || upd, who, ": keep_dw=False needs update_lr > 0 (update-only step)");
+  // compute_dw=False (the activation exchange forms the fc step): no dW product, the weight only read
+  TORCH_CHECK(compute_dw || (!upd && !given(mom_buf)), who, ": update_lr / mom_buf need compute_dw");
+  keep_dw = keep_dw && compute_dw;
   Tensor dW;  // undefined (None) for an update-only step
   if (keep_dw && given(dw_out)) {
     need(*dw_out, at::kFloat, {NC, d.K()}, "dw_out");
@@ -1099,6 +1125,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> fused_head_wide_backw
                          dlogits.data_ptr<float>(), (int)B, (int)NC, dbfc.data_ptr<float>(), (float)scale,
                          m && !ypart_done ? m + kMagParts : nullptr, (int)mag_ypart_count(), gp, 32 * nblk, m, st);
   check_launches(who);
+  if (!compute_dw) dW = at::empty({0}, wfc.options());  // (as fused_head_backward)
   return {dW, dbfc, dgamma, dbeta, g2m, kbuf};
 }
 
@@ -1505,7 +1532,7 @@ TORCH_LIBRARY_FRAGMENT(tdsa, m) {
       "Tensor(e!) wfc, Tensor wmax, int P, Tensor(a!)? dw_out, float scale, float update_lr=0.0, "
       "Tensor(b!)? dbfc_out=None, Tensor(c!)? dg_out=None, Tensor(d!)? dbe_out=None, bool keep_dw=True, "
       "Tensor(h!)? mag=None, bool ypart_done=False, Tensor(i!)? mom_buf=None, float weight_decay=0.0, "
-      "float momentum=0.0, float dampening=0.0, bool nesterov=False, bool first_step=False) "
+      "float momentum=0.0, float dampening=0.0, bool nesterov=False, bool first_step=False, bool compute_dw=True) "
       "-> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)",
       &fused_head_wide_backward);
   m.def("head_bwd_workspace(int B, int P) -> int", &head_bwd_workspace);

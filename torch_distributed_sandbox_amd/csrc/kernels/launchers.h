@@ -286,11 +286,16 @@ int tds_head_wide_fwd(const unsigned short* ya, TdsYaDec yd, const float* Wfc, c
                       double* partial, uint32_t* wmax, float* logits, int B, int Q, int NC, hipStream_t st);
 // one pass over all channels on tds_head_bwd_pb's grid (tds_head_bwd_pb_nblk bands per channel):
 // partial [32][nblk][4], gpart [32][nblk], g2m / g2inv / hf / hm as there.  dW and / or Wupd (the
-// step in place); hm needs Wupd and lr > 0.
+// step in place); hm needs Wupd and lr > 0.  Neither dW nor Wupd: the no-dW form (no dW product, the
+// weight only read), every other output bitwise as with dW.
 int tds_head_wide_bwd(const unsigned short* ya, TdsYaDec yd, const float* Wfc, const float* aff2, const float* dlogits,
                       const uint32_t* wmax, unsigned short* g2m, float* g2inv, double* partial, uint32_t* gpart,
                       float* dW, float* Wupd, int B, int Q, int NC, float scale, float lr, hipStream_t st,
                       const TdsHeadBwdFin* hf = nullptr, const TdsHeadMom* hm = nullptr);
+// tds_head_upd_pb for 11 .. 64 classes and <= 16 images per rank (head_wide_upd_kernel, fp32 MFMA):
+// ya_all [nranks][B][32][PB] fp16 contiguous, rec / dl / W / out / mode as there
+int tds_head_wide_upd(const unsigned short* ya_all, const float* rec, int nranks, const float* dl, const float* W,
+                      float* out, int B, int Q, int NC, float scale, float lr, int mode, hipStream_t st);
 
 // ---- zs_exchange.hip (zero-suppressed fc-input rows, parallel/zs.py)
 int64_t tds_zs_npages(int64_t n);

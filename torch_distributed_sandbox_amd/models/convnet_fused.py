@@ -352,7 +352,8 @@ class _Head(torch.autograd.Function):
             stats2, aff2 = bn_a, bn_b
         wmax = None
         if wfc.shape[0] > 10:
-            # 11 .. 64 classes: the wide head's ops (fp32 MFMA, head_wide.hip); no fc exchange (forward below)
+            # 11 .. 64 classes: the wide head's ops (fp32 MFMA, head_wide.hip); an fc exchange was begun
+            # from the pooled input or there is none (forward below): no fc input rows are written
             if upd is not None:
                 upd()
             if not link.bn_done:
@@ -435,10 +436,12 @@ class _Head(torch.autograd.Function):
             ex.chunked_done(dw, db)
             dW = dbfc = None
         elif ex is not None:
-            # fc gradients come from the activation exchange (parallel/factored.py)
-            _, _, dg2, dbe2, g2m, kbuf = ops.fused_head_backward(dlogits, ya, stats2, aff2, b2, g2, wfc, P, dw_out=None,
-                                                                 scale=1.0, compute_dw=False, mag=ctx.link.mag,
-                                                                 ypart_done=ctx.link.bn_done)
+            # fc gradients come from the activation exchange (parallel/factored.py): the no-dW forms
+            head_bwd, w_args = ops.fused_head_backward, (wfc,)
+            if ctx.wmax is not None:
+                head_bwd, w_args = ops.fused_head_wide_backward, (wfc, ctx.wmax)
+            _, _, dg2, dbe2, g2m, kbuf = head_bwd(dlogits, ya, stats2, aff2, b2, g2, *w_args, P, dw_out=None, scale=1.0,
+                                                  compute_dw=False, mag=ctx.link.mag, ypart_done=ctx.link.bn_done)
             ex.defer(dlogits)
             dW = dbfc = None
         else:
@@ -519,15 +522,19 @@ def forward(model, x):
     # agrees for the sharded path under source "pooled-sharded": ya's channel planes go to their
     # owners from here, and the head forward allocates no x_out and calls no ex.begin
     ex = factored.get(fc.weight)
-    if fc.out_features > 10:
-        # no fc exchange above ten classes (the wide head writes dW into the bucket): declined per
-        # step like a ready() that says no -- an exchange only claims the gradient once begun
-        ex = None
     B = x.shape[0]
-    if ex is not None and link.bn_done and B <= 8 and ex.ready(B) and ex.pooled(B):
+    # above ten classes (the wide head, up to 16 images): the activation path from the pooled input only
+    # (ops.head_update_pooled's MFMA kernel); the wide head writes no fc input rows
+    wide = fc.out_features > 10
+    if (ex is not None and link.bn_done and B <= (16 if wide else 8) and ex.ready(B) and ex.pooled(B)
+            and (not wide or ex.planned(B) == "activations")):
         ops = _ext.ops()
         ex.begin_pooled(ya, ops.head_pooled_record(bn_b, conv2.bias, link.mag), y2.shape[1])
         link.pooled = True
+    if wide and not link.pooled:
+        # declined for this step like a ready() that says no (the wide head writes dW into the bucket):
+        # an exchange only claims the gradient once begun
+        ex = None
     # the fc update may still be running on DDP's side stream (overlap_optimizer), or deferred to
     # here (the activation exchange's update sweep, factored.py _DeferredUpdate): wait / queue it now, after
     # the convolutions were queued, not before.  A grouped update goes to the head forward, which

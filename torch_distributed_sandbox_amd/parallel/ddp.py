@@ -328,14 +328,15 @@ class DistributedDataParallel(nn.Module):
         """This package's Linear layers (their forward routes through ops.functional.linear /
         the fused head, which implement the exchange) big enough that exchanging activations
         can beat all-reducing the weight gradient; the decision itself is made per step
-        from the batch rows."""
+        from the batch rows.  Up to 64 rows: above 16 only the fused plan's wide head exchanges
+        (from its pooled input; parallel/factored.py ``WIDE_ROWS``), every other path declines."""
         from ..ops.modules import Linear as TdsLinear
 
         out = []
         for m in module.modules():
             if isinstance(m, TdsLinear):
                 w, b = m.weight, m.bias
-                if w.requires_grad and w.numel() >= (1 << 20) and w.shape[0] <= 16 and (b is None or b.requires_grad):
+                if w.requires_grad and w.numel() >= (1 << 20) and w.shape[0] <= 64 and (b is None or b.requires_grad):
                     out.append(m)
         return out
 

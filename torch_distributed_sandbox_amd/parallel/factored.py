@@ -60,7 +60,8 @@ affine of that rank's batch, ya's decode, the conv bias).  The ranks all-gather 
 constants right after the conv2 forward wrote them -- before the head forward starts -- and every
 rank forms the fc step from them (``ops.head_update_pooled``), recomputing each rank's X with that
 rank's constants and the head forward's own arithmetic: bitwise the rows the dense exchange would
-have sent.  ``link_bytes`` prices it at x_ratio 0.5.
+have sent.  ``link_bytes`` prices it at x_ratio 0.5.  A layer of more than 16 rows (the wide head, up
+to 64 classes) exchanges this way or not at all (``WIDE_ROWS``).
 
 Pooled sharded source (``source="pooled-sharded"``, opt-in): the sharded path from the same pooled
 input.  The fc weight's columns are ordered (channel, row, column) and a (image, channel) plane of
@@ -228,6 +229,7 @@ class ActivationExchange:
 
     CAP_MARGIN = 1.03     # value capacity over the largest recent non-zero count
     CAP_ROUND = 1 << 16   # capacities rounded up to 64 Ki elements (stable allocations)
+    WIDE_ROWS = 16        # above: no rows / sharded / chunked exchange (their kernels stop at 16 outputs)
 
     def __init__(self, weight: torch.nn.Parameter, bias: Optional[torch.nn.Parameter], group, world: int,
                  mode: str, set_skip, weight_view, bias_view, chunks: int = 1, compress: bool = True,
@@ -244,6 +246,9 @@ class ActivationExchange:
         # it (begin_pooled); "rows": always the fc input rows X (begin / begin_groups);
         # "pooled-sharded": as "pooled", and the sharded path takes the pooled input too
         self.source = source
+        # a layer of more than WIDE_ROWS rows (the fused ConvNet's wide head, up to 64 classes) runs the
+        # activation path from the pooled input or nothing (``path``, ``begin``)
+        self.wide = weight.shape[0] > self.WIDE_ROWS
         self._step: Optional[_Step] = None  # the running step's record; None between steps
         self._set_skip, self._wview, self._bview = set_skip, weight_view, bias_view
         self.armed = False
@@ -277,6 +282,16 @@ class ActivationExchange:
     def path(self, rows: int) -> Optional[str]:
         """"activations" | "sharded" | "chunked" for a step with ``rows`` local rows, or None
         (plain bucket all-reduce)."""
+        if self.wide:
+            # more than WIDE_ROWS rows: only the activation path from the pooled input, which the
+            # fused plan starts (begin_pooled); every other path, the rows source included, declines
+            if self.mode not in ("auto", "activations") or not self.pooled_capable():
+                return None
+            if self.mode == "auto":
+                out_f, in_f = self.weight.shape
+                if self.world <= 1 or choose_path(rows, out_f, in_f, self.world, x_ratio=0.5) != "activations":
+                    return None
+            return "activations"
         if self.mode in ("activations", "sharded"):
             return self.mode
         if self.mode == "chunked":
@@ -488,9 +503,10 @@ class ActivationExchange:
     def begin(self, x2d: Optional[torch.Tensor], rows: Optional[int] = None) -> bool:
         """Called from the layer's forward (possibly inside an autograd Function,
         i.e. under no_grad) with its [rows, in] input (None with ``rows`` when the chunked
-        path, which needs no X, was agreed by ``ready``).  Every rank has the same rows."""
+        path, which needs no X, was agreed by ``ready``).  Every rank has the same rows.  A wide
+        layer declines: its exchange starts from the pooled input only (``begin_pooled``)."""
         path = self._eligible(x2d.shape[0] if x2d is not None else int(rows))
-        if path is None:
+        if path is None or self.wide:
             return False
         from . import distributed as tdist
 
