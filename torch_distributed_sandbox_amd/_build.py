@@ -61,6 +61,8 @@ HIP_FILE_FLAGS = {
     "x_autocorr.hip": ["-fno-slp-vectorize"],
     "conv2_bwd.hip": ["-fno-slp-vectorize"],
     "conv2_fwd2.hip": ["-fno-slp-vectorize"],
+    # MFMA beside per-element f32 VALU (the 81-tap filter), as the conv2 kernels; results into VGPRs
+    "l1_dgrad.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"],
     # the wide head's epilogues read every MFMA tile back (as above); no packed fp32 VALU: its sums and
     # SGD steps are scalar fp32 by contract (bitwise the same values in every weight form)
     "head_wide.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-Xclang", "-target-feature", "-Xclang",

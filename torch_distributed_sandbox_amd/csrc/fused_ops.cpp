@@ -1296,7 +1296,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> fused_l1_backward(const Tensor& dp1, 
                                                              const c10::optional<Tensor>& dw_out,
                                                              const c10::optional<Tensor>& db_out,
                                                              const c10::optional<Tensor>& dg_out,
-                                                             const c10::optional<Tensor>& dbe_out) {
+                                                             const c10::optional<Tensor>& dbe_out,
+                                                             const c10::optional<Tensor>& bsum_out) {
   TORCH_CHECK(x.dim() == 4 && x.size(1) == 1, "fused_l1_backward: x");
   const int64_t B = x.size(0), H = x.size(2), W = x.size(3), P = H / 2;
   const bool levels = x.scalar_type() == at::kByte;
@@ -1324,7 +1325,10 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> fused_l1_backward(const Tensor& dp1, 
   // in one workgroup, l1 backward 0.172 ms vs 0.131 + 2 x 0.007, r5_s3)
   tds_l1_bwd(x.data_ptr(), levels, dp1.data_ptr(), reinterpret_cast<const uint32_t*>(dp1_dec.data_ptr<int>()),
              p1.data_ptr(), idx1.data_ptr<uint8_t>(), partial.data_ptr<double>(), nwg, (int)B, (int)H, (int)W, st);
-  auto bsum = at::empty({16 * 27}, x.options().dtype(at::kDouble));
+  // (bsum_out: the caller keeps the 432 fp64 sums, which fused_l1_input_grad's coefficients are formed from)
+  const bool keep_sums = bsum_out.has_value() && bsum_out->defined();
+  if (keep_sums) need(*bsum_out, at::kDouble, {16 * 27}, "bsum_out");
+  auto bsum = keep_sums ? *bsum_out : at::empty({16 * 27}, x.options().dtype(at::kDouble));
   // the partials' reduction and the closed-form gradients in one launch (tds_l1_reduce_finalize)
   if (!tds_l1_reduce_finalize(partial.data_ptr<double>(), rows, bsum.data_ptr<double>(), gram.data_ptr<double>(),
                               B * H * W, w1.data_ptr<float>(), b1.data_ptr<float>(), g, stats1.data_ptr<float>(),
@@ -1337,6 +1341,39 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> fused_l1_backward(const Tensor& dp1, 
   }
   check_launches("fused_l1_backward");
   return {dw1, db1, dg, dbe};
+}
+
+// The layer-1 input gradient dL/dx (kernels/l1_dgrad.hip) of an fp32 image, after fused_l1_backward:
+// bsum is that op's bsum_out (sum dz and sum dz xpatch per channel, fp64), from which BN1's
+// backward coefficients are formed.  Two launches: the coefficient tables, then the tile kernel.
+Tensor fused_l1_input_grad(const Tensor& dp1, const Tensor& dp1_dec, const Tensor& x, const Tensor& idx1,
+                           const Tensor& w1, const Tensor& b1, const c10::optional<Tensor>& gamma1,
+                           const Tensor& stats1, const Tensor& bsum) {
+  TORCH_CHECK(x.dim() == 4 && x.size(1) == 1, "fused_l1_input_grad: x");
+  const int64_t B = x.size(0), H = x.size(2), W = x.size(3), P = H / 2;
+  TORCH_CHECK(H == W && H >= 16 && H % 4 == 0 && H <= 65520 && B >= 1 && B <= 32,
+              "fused_l1_input_grad: needs a square image, 16 <= H <= 65520, H % 4 == 0, batch <= 32; got ", x.sizes());
+  need(x, at::kFloat, {B, 1, H, W}, "x (an fp32 image: a uint8 level batch has no gradient)");
+  need(dp1, at::kHalf, {B, P, (W / 2 + 3) / 4, 16, 4}, "dp1h (fused_conv2_backward_y2's)");
+  TORCH_CHECK(dp1_dec.is_cuda() && dp1_dec.scalar_type() == at::kInt && dp1_dec.numel() >= 1,
+              "dp1_dec: the dp1h decode factor (int32 GPU view of mag[kMagScales + 4])");
+  need(idx1, at::kByte, {B, P, P, 16}, "idx1");
+  need(w1, at::kFloat, {16, 1, 5, 5}, "conv1.weight");
+  need(b1, at::kFloat, {16}, "conv1.bias");
+  need(stats1, at::kFloat, {32}, "stats1");
+  need(bsum, at::kDouble, {16 * 27}, "bsum (fused_l1_backward's bsum_out)");
+  const float* g = optf(gamma1, 16, "bn1.weight");
+  for (const Tensor* t : {&dp1, &dp1_dec, &idx1, &w1, &b1, &stats1, &bsum})
+    TORCH_CHECK(t->device() == x.device(), "fused_l1_input_grad: every tensor on x's device");
+  c10::DeviceGuard guard(x.device());
+  hipStream_t st = stream_of(x);
+  auto coef = at::empty({(int64_t)tds_l1_dgrad_coef_numel()}, x.options());
+  auto dx = at::empty_like(x);
+  tds_l1_dgrad(x.data_ptr<float>(), dp1.data_ptr(), reinterpret_cast<const uint32_t*>(dp1_dec.data_ptr<int>()),
+               idx1.data_ptr<uint8_t>(), bsum.data_ptr<double>(), w1.data_ptr<float>(), b1.data_ptr<float>(), g,
+               stats1.data_ptr<float>(), coef.data_ptr<float>(), dx.data_ptr<float>(), (int)B, (int)H, (int)W, st);
+  check_launches("fused_l1_input_grad");
+  return dx;
 }
 
 // ---------------------------------------------------------------- zero-suppressed X exchange
@@ -1567,8 +1604,12 @@ TORCH_LIBRARY_FRAGMENT(tdsa, m) {
   m.def(
       "fused_l1_backward(Tensor dp1, Tensor dp1_dec, Tensor x, Tensor p1, Tensor idx1, Tensor w1, Tensor b1, Tensor? gamma1, "
       "Tensor stats1, Tensor gram, float scale, Tensor(a!)? dw_out=None, Tensor(b!)? db_out=None, "
-      "Tensor(c!)? dg_out=None, Tensor(d!)? dbe_out=None) -> (Tensor, Tensor, Tensor, Tensor)",
+      "Tensor(c!)? dg_out=None, Tensor(d!)? dbe_out=None, Tensor(e!)? bsum_out=None) -> (Tensor, Tensor, Tensor, Tensor)",
       &fused_l1_backward);
+  m.def(
+      "fused_l1_input_grad(Tensor dp1, Tensor dp1_dec, Tensor x, Tensor idx1, Tensor w1, Tensor b1, Tensor? gamma1, "
+      "Tensor stats1, Tensor bsum) -> Tensor",
+      &fused_l1_input_grad);
   m.def("launch_probe(Tensor like, int lds_bytes, int threads) -> ()", &launch_probe);
   m.def("set_cu_reserve(int n) -> ()", &set_cu_reserve);
   m.def("cu_reserve() -> int", &cu_reserve);

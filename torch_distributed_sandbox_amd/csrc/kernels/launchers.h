@@ -190,6 +190,13 @@ bool tds_l1_reduce_gram(const double* ac_part, int nchunk, double* ac_sum, doubl
 void tds_l1_finalize(const double* bwd_sum, const double* gram, int64_t n, const float* w1, const float* b1,
                      const float* gamma1, const float* stats1, float* dw1, float* db1, float* dgamma1, float* dbeta1,
                      float scale, hipStream_t st);
+// ---- l1_dgrad.hip: the layer-1 input gradient dx [B,1,H,W] of an fp32 image from dp1h, idx1 and the
+// layer-1 backward's fp64 sums bwd_sum [16][27] (two launches: the coefficients into coef
+// [tds_l1_dgrad_coef_numel() floats], then the tile kernel)
+int tds_l1_dgrad_coef_numel();
+void tds_l1_dgrad(const float* x, const void* dp1h, const uint32_t* dp1_dec, const uint8_t* idx1, const double* bwd_sum,
+                  const float* w1, const float* b1, const float* gamma1, const float* stats1, float* coef, float* dx,
+                  int B, int H, int W, hipStream_t st);
 
 // ---- inference.hip (the inference plan's small launches)
 int tds_x_absmax_num_wg(int64_t n4);  // partial words tds_x_absmax writes for n4 float4

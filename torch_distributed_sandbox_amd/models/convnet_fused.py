@@ -6,7 +6,9 @@ fp32 NCHW tensors.  This plan runs the network as three
 autograd Functions over NHWC fp16 / uint8-level activations (kernels in
 ``csrc/kernels/convnet_fused.hip``, ``conv2_fwd2.hip``, ``conv2_bwd.hip``, ``head_pb.hip``):
 
-``_Layer1``  x -> p1            conv1 + BN1(batch stats) + ReLU + pool, conv1 never stored; p1 in fp16
+``_Layer1``  x -> p1            conv1 + BN1(batch stats) + ReLU + pool, conv1 never stored; p1 in fp16;
+                                an fp32 x that requires a gradient gets dL/dx from its backward
+                                (``l1_dgrad.hip``; no cost otherwise)
 ``_Conv2``   p1 -> y2, ya       conv2 (TF32-class fp16 MFMA) with BN2 batch-stat partials and the 2x2
                                 max-pool (ya = y2 at each window's argmax, resolved by the sign
                                 of BN2's gamma, in fp16 as y2h stores it) fused; its backward
@@ -231,9 +233,17 @@ class _Layer1(torch.autograd.Function):
         dp1, dp1_dec = ctx.link1.dp1, ctx.link1.dp1_dec
         ctx.link1.dp1 = ctx.link1.dp1_dec = None
         outs = _sinks(ctx, ctx.params, 1)
-        dw1, db1, dg1, dbe1 = _ext.ops().fused_l1_backward(dp1, dp1_dec, x, p1, idx1, w1, b1, g1, stats1, gram, 1.0,
-                                                           *outs)
-        return None, dw1, db1, dg1, dbe1, None, None, None, None, None, None
+        ops = _ext.ops()
+        if not (ctx.needs_input_grad[0] and x.is_floating_point()):
+            dw1, db1, dg1, dbe1 = ops.fused_l1_backward(dp1, dp1_dec, x, p1, idx1, w1, b1, g1, stats1, gram, 1.0, *outs)
+            return None, dw1, db1, dg1, dbe1, None, None, None, None, None, None
+        # dL/dx (csrc/kernels/l1_dgrad.hip): BN1's backward coefficients come from the layer-1 backward's
+        # fp64 sums, which that op leaves in bsum; dp1 stays referenced until the launch is queued
+        bsum = torch.empty(16 * 27, device=x.device, dtype=torch.float64)
+        dw1, db1, dg1, dbe1 = ops.fused_l1_backward(dp1, dp1_dec, x, p1, idx1, w1, b1, g1, stats1, gram, 1.0, *outs,
+                                                    bsum)
+        dx = ops.fused_l1_input_grad(dp1, dp1_dec, x, idx1, w1, b1, g1, stats1, bsum)
+        return dx, dw1, db1, dg1, dbe1, None, None, None, None, None, None
 
 
 class _Layer2Link:
