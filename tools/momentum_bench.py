@@ -13,7 +13,12 @@ the line holds ms per step over ``--repeats`` timed windows of ``--steps`` steps
 excluded) and the peak memory allocated.  Only the public API is used, so the same file measures a
 tree from before the momentum fast paths existed.  Needs a GPU: a timing has no CPU fallback.
 
+``--exchange`` forces the fc gradient exchange (``grad_exchange="activations"``) on an ``rccl-native``
+process group of one rank: the step then takes the multi-GPU route -- the pooled update kernels -- with
+one rank's images; ``--num-classes 26`` puts the wide head (11 .. 64 classes) there.
+
     python tools/momentum_bench.py --image-size 3000 --batch-size 5
+    python tools/momentum_bench.py --exchange --num-classes 26
 """
 from __future__ import annotations
 
@@ -49,8 +54,17 @@ def _child(a):
     dev = torch.device("cuda", 0)
     H, B = a.image_size, a.batch_size
     torch.manual_seed(0)
-    model = ConvNet(image_shape=(H, H), device=dev, mode="fused")
-    ddp = DistributedDataParallel(model, device_ids=[0], overlap_optimizer=True)
+    kw = {}
+    if a.exchange:
+        from torch_distributed_sandbox_amd.parallel import distributed as dist
+        from torch_distributed_sandbox_amd.parallel import launch
+
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", launch.find_free_port())
+        dist.init_process_group("rccl-native", rank=0, world_size=1)
+        kw["grad_exchange"] = "activations"
+    model = ConvNet(num_classes=a.num_classes, image_shape=(H, H), device=dev, mode="fused")
+    ddp = DistributedDataParallel(model, device_ids=[0], overlap_optimizer=True, **kw)
     opt = ddp.attach_optimizer(SGD(model.parameters(), a.lr, **SETS[a.child]))
     crit = CrossEntropyLoss()
     src = torch.randint(0, 256, (B, 28, 28), dtype=torch.uint8, device=dev)
@@ -80,7 +94,10 @@ def _child(a):
     torch.cuda.synchronize()
     print(json.dumps({"ms_per_step": ms, "peak_mem_gb": torch.cuda.max_memory_allocated(dev) / 1e9,
                       "fc_grad_is_none": model.fc.weight.grad is None, "final_loss": float(loss.item()),
+                      "fc_grad_path": ddp.fc_grad_path() if hasattr(ddp, "fc_grad_path") else None,
                       "device": torch.cuda.get_device_name(dev)}), flush=True)
+    if a.exchange:
+        dist.destroy_process_group()
 
 
 def main(argv=None):
@@ -92,16 +109,23 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--plain", action="store_true", help="also time SGD(lr)")
+    ap.add_argument("--num-classes", type=int, default=10)
+    ap.add_argument("--exchange", action="store_true",
+                    help='force grad_exchange="activations" on rccl-native at world size 1')
+    ap.add_argument("--sets", default="momentum,nesterov_wd", help="optimizer sets to run, comma-separated")
     ap.add_argument("--time-limit", type=float, default=180.0, help="seconds per optimizer set (its own process)")
     ap.add_argument("--child", default=None, choices=list(SETS), help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
     if a.child:
         return _child(a)
     rec = {"metric": "momentum_bench", "image_size": a.image_size, "batch_size": a.batch_size, "lr": a.lr,
-           "steps": a.steps, "warmup": a.warmup, "repeats": a.repeats}
+           "steps": a.steps, "warmup": a.warmup, "repeats": a.repeats, "num_classes": a.num_classes,
+           "exchange": a.exchange}
     base = [sys.executable, os.path.abspath(__file__)] + [f"--{k.replace('_', '-')}={getattr(a, k)}" for k in
-                                                           ("image_size", "batch_size", "lr", "steps", "warmup", "repeats")]
-    for name in (["plain"] if a.plain else []) + ["momentum", "nesterov_wd"]:
+                                                           ("image_size", "batch_size", "lr", "steps", "warmup", "repeats",
+                                                            "num_classes")]
+    base += ["--exchange"] if a.exchange else []
+    for name in (["plain"] if a.plain else []) + [s for s in a.sets.split(",") if s]:
         try:
             p = subprocess.run(base + ["--child", name], capture_output=True, text=True, timeout=a.time_limit, cwd=ROOT)
         except subprocess.TimeoutExpired:

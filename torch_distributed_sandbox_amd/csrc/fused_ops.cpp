@@ -759,7 +759,7 @@ HeadDims head_wide_upd_dims(const Tensor& ya_all, const Tensor& wfc, int64_t P, 
 // classes the wide head's (the shard form stays at ten).
 void head_update(const char* who, bool shard, const Tensor& dl_all, const Tensor& ya, const Tensor& rec_all,
                  const Tensor& wfc, const c10::optional<Tensor>& out, int64_t P, int64_t c0, int64_t c1, double scale,
-                 double lr, int64_t mode) {
+                 double lr, int64_t mode, const TdsHeadMom* hm = nullptr) {
   TORCH_CHECK(c0 >= 0 && c0 < c1 && c1 <= 32, who, ": needs 0 <= c0 < c1 <= 32");
   const bool wide = !shard && wfc.dim() == 2 && wfc.size(0) > 10;
   const HeadDims d = wide ? head_wide_upd_dims(ya, wfc, P, who)
@@ -783,13 +783,13 @@ void head_update(const char* who, bool shard, const Tensor& dl_all, const Tensor
   const int rc =
       wide  ? tds_head_wide_upd(ya_out(ya), rec_all.data_ptr<float>(), (int)Wr, dl_all.data_ptr<float>(),
                                 wfc.data_ptr<float>(), o, (int)d.B, (int)d.Q, (int)d.NC, (float)scale, (float)lr,
-                                (int)mode, stream_of(wfc))
+                                (int)mode, stream_of(wfc), hm)
       : shard ? tds_head_upd_pb_shard(ya_out(ya), rec_all.data_ptr<float>(), (int)Wr, dl_all.data_ptr<float>(),
                                     wfc.data_ptr<float>(), o, (int)d.B, (int)d.Q, (int)d.NC, (int)c0, (int)c1,
                                     (float)scale, (float)lr, (int)mode, stream_of(wfc))
             : tds_head_upd_pb(ya_out(ya), d.B * 32 * pb_plane(P), rec_all.data_ptr<float>(), (int)Wr,
                               dl_all.data_ptr<float>(), wfc.data_ptr<float>(), o, (int)d.B, (int)d.Q, (int)d.NC,
-                              (float)scale, (float)lr, (int)mode, stream_of(wfc));
+                              (float)scale, (float)lr, (int)mode, stream_of(wfc), hm);
   TORCH_CHECK(rc == 0, who, ": unsupported shape");
   check_launches(who);
 }
@@ -797,6 +797,29 @@ void head_update(const char* who, bool shard, const Tensor& dl_all, const Tensor
 void head_update_pooled(const Tensor& dl_all, const Tensor& ya_all, const Tensor& rec_all, const Tensor& wfc,
                         const c10::optional<Tensor>& out, int64_t P, double scale, double lr, int64_t mode) {
   head_update("head_update_pooled", false, dl_all, ya_all, rec_all, wfc, out, P, 0, 32, scale, lr, mode);
+}
+
+// head_update_pooled's mode 0 with torch's whole SGD rule (momentum, dampening, weight decay, nesterov;
+// kernels/common.h sgd_rule_step): wfc and its momentum buffer mbuf are stepped in place on d = scale *
+// dl_all^T X, the value mode 1 writes -- bitwise mode 1 followed by the optimizer's flat sweep, without
+// dW in memory.  first_step: this step creates the buffer, its contents are ignored.  A weight of 11 ..
+// 64 rows takes at most 128 images over all ranks (one launch holds the whole sum).
+void head_update_pooled_step(const Tensor& dl_all, const Tensor& ya_all, const Tensor& rec_all, const Tensor& wfc,
+                             const Tensor& mbuf, int64_t P, double scale, double lr, double weight_decay,
+                             double momentum, double dampening, bool nesterov, bool first_step) {
+  const char* who = "head_update_pooled_step";
+  TORCH_CHECK(wfc.defined() && wfc.is_cuda(), who, ": fc.weight must be a GPU tensor");
+  need(mbuf, at::kFloat, wfc.sizes().vec(), "mbuf");
+  TORCH_CHECK(mbuf.device() == wfc.device(), who, ": mbuf is on another device than fc.weight");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(mbuf.data_ptr()) % 16 == 0, who, ": mbuf must be 16-B aligned");
+  const char* m0 = static_cast<const char*>(mbuf.data_ptr());
+  const char* w0 = static_cast<const char*>(wfc.data_ptr());
+  const int64_t nbytes = (int64_t)wfc.nbytes();
+  TORCH_CHECK(m0 + nbytes <= w0 || w0 + nbytes <= m0, who, ": mbuf aliases fc.weight");
+  TORCH_CHECK(momentum != 0.0, who, ": needs momentum != 0 (head_update_pooled mode 0 is the plain step)");
+  const TdsHeadMom hm{mbuf.data_ptr<float>(), (float)weight_decay, (float)momentum, (float)dampening, nesterov,
+                      first_step};
+  head_update(who, false, dl_all, ya_all, rec_all, wfc, c10::nullopt, P, 0, 32, scale, lr, 0, &hm);
 }
 
 // The shard form (the sharded exchange's "pooled-sharded" source): this rank owns the fc columns of
@@ -1586,6 +1609,11 @@ TORCH_LIBRARY_FRAGMENT(tdsa, m) {
       "head_update_pooled(Tensor dl_all, Tensor ya_all, Tensor rec_all, Tensor(a!) wfc, Tensor(b!)? out, int P, "
       "float scale, float lr, int mode) -> ()",
       &head_update_pooled);
+  m.def(
+      "head_update_pooled_step(Tensor dl_all, Tensor ya_all, Tensor rec_all, Tensor(a!) wfc, Tensor(b!) mbuf, int P, "
+      "float scale, float lr, float weight_decay, float momentum, float dampening, bool nesterov, bool first_step) "
+      "-> ()",
+      &head_update_pooled_step);
   m.def(
       "head_update_pooled_shard(Tensor dl_all, Tensor ya_sh, Tensor rec_all, Tensor(a!) wfc, Tensor(b!)? out, int P, "
       "int c0, int c1, float scale, float lr, int mode) -> ()",

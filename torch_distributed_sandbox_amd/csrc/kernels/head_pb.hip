@@ -696,11 +696,19 @@ __global__ __launch_bounds__(HP_THREADS) void head_bwd_pb_kernel(
 //   MODE 0: W -= lr * scale * sum_m dl[m] (x) X_m        (update only, the SGD step)
 //   MODE 1: out = scale * sum_m dl[m] (x) X_m             (dW)
 //   MODE 2: out += scale * sum_m dl[m] (x) X_m
+//   MODE 3: W, mbuf = torch's SGD rule on d = scale * sum_m dl[m] (x) X_m  (common.h sgd_rule_step; the
+//           value MODE 1 stores, so bitwise MODE 1 followed by the flat sweep; no dW is written)
 // with X_m recomputed from rank r's ya as its head forward did (m = r * NB + b; rec[r]: aff2 [64] |
 // ya scale words [3] | pad | b2 [32] | pad): the same v_fma_mix arithmetic on the same values, so
 // X is bitwise the rows that forward multiplied by the weight.  Workgroup = (channel, band of the
 // backward's HP_BAND_B block rows), 4 columns of one pooled row per thread as the head kernels;
 // per chunk the weight 4-groups are loaded once and every rank's images stream past them.
+// MODE 3 (out = W): the momentum buffer mbuf has the weight's layout and addressing, as in the head
+// backward's MOM form -- its 4-groups are loaded at HPRow::ldoff, edge groups re-aligned (hp_fix_b),
+// stored through hp_store4 inside nvalid only.  They are loaded in the epilogue, after the rank / image
+// stream, when the ya registers are dead, HP_MOM_AHEAD classes ahead of their use: ten groups held beside
+// acc[10][4] and the weight's across the stream would cost a wave per SIMD.  A creating step
+// (rule.first) loads none.  (mbuf and rule are trailing arguments the other modes never read.)
 constexpr int HP_REC = 128;  // floats per rank record
 
 template <int NB, int MODE>
@@ -708,7 +716,7 @@ __global__ __launch_bounds__(HP_THREADS) void head_upd_pb_kernel(const unsigned 
                                                                  int64_t ya_rs, const float* __restrict__ rec,
                                                                  int nranks, const float* __restrict__ dl,
                                                                  const float* W, float* out, PBGeom g, int NC,
-                                                                 float scale, float lr) {
+                                                                 float scale, float lr, float* mbuf, SgdRule rule) {
   const HPGrid hg = hp_grid_b(g);
   const int c = (int)blockIdx.x / hg.per_channel(), band = (int)blockIdx.x - c * hg.per_channel();
   const int Q = g.Q;
@@ -763,8 +771,23 @@ __global__ __launch_bounds__(HP_THREADS) void head_upd_pb_kernel(const unsigned 
       }
     }
     const HPRow rw(g, th, c, R);
+    // MODE 3: the buffer's groups, HP_MOM_AHEAD classes ahead; the load of class j + HP_MOM_AHEAD
+    // precedes the stores of class j in program order
+    [[maybe_unused]] float4 mb[HP_MOM_AHEAD];
+    [[maybe_unused]] const int64_t cls = (int64_t)32 * Q * (int64_t)Q;
+    if constexpr (MODE == 3) {
+#pragma unroll
+      for (int j = 0; j < HP_MOM_AHEAD; ++j)
+        mb[j] = rule.first ? make_float4(0.f, 0.f, 0.f, 0.f) : hp_ld4(mbuf + (j < NC ? j : 0) * cls + rw.ldoff);
+    }
 #pragma unroll
     for (int j = 0; j < 10; ++j) {
+      [[maybe_unused]] float4 bcur;
+      if constexpr (MODE == 3) {
+        bcur = mb[j % HP_MOM_AHEAD];
+        if (j + HP_MOM_AHEAD < 10 && !rule.first)
+          mb[j % HP_MOM_AHEAD] = hp_ld4(mbuf + (j + HP_MOM_AHEAD < NC ? j + HP_MOM_AHEAD : 0) * cls + rw.ldoff);
+      }
       if (j < NC) {
         const float4 d = make_float4(scale * acc[j][0], scale * acc[j][1], scale * acc[j][2], scale * acc[j][3]);
         if constexpr (MODE == 0) {
@@ -772,6 +795,15 @@ __global__ __launch_bounds__(HP_THREADS) void head_upd_pb_kernel(const unsigned 
           hp_store4(out, g, rw, j, make_float4(w.x - lr * d.x, w.y - lr * d.y, w.z - lr * d.z, w.w - lr * d.w));
         } else if constexpr (MODE == 1) {
           hp_store4(out, g, rw, j, d);
+        } else if constexpr (MODE == 3) {  // torch SGD with momentum / weight decay, both in place
+          const float4 w = cur.w[j], bo = hp_fix_b(bcur, rw.sh);
+          float4 bn, wn;
+          wn.x = sgd_rule_step(w.x, d.x, bo.x, rule, true, bn.x);
+          wn.y = sgd_rule_step(w.y, d.y, bo.y, rule, true, bn.y);
+          wn.z = sgd_rule_step(w.z, d.z, bo.z, rule, true, bn.z);
+          wn.w = sgd_rule_step(w.w, d.w, bo.w, rule, true, bn.w);
+          hp_store4(mbuf, g, rw, j, bn);
+          hp_store4(out, g, rw, j, wn);
         } else if (rw.nvalid > 0) {
           float* p = out + (int64_t)j * 32 * Q * (int64_t)Q + rw.off;
           const float e[4] = {d.x, d.y, d.z, d.w};
@@ -914,15 +946,22 @@ void tds_head_pooled_record(const float* aff2, const float* b2, const uint32_t* 
 }
 
 int tds_head_upd_pb(const unsigned short* ya_all, int64_t ya_rs, const float* rec, int nranks, const float* dl,
-                    const float* W, float* out, int B, int Q, int NC, float scale, float lr, int mode, hipStream_t st) {
+                    const float* W, float* out, int B, int Q, int NC, float scale, float lr, int mode, hipStream_t st,
+                    const TdsHeadMom* hm) {
   if (B < 1 || B > HP_MAXB || NC < 1 || NC > 10 || Q < 4 || nranks < 1 || mode < 0 || mode > 2) return -1;
+  // the rule form: mode 0's in-place step of the whole weight, with its buffer
+  if (hm != nullptr && (hm->buf == nullptr || mode != 0 || out != W || !(lr > 0.f))) return -2;
   const PBGeom g = pb_geom(Q);
   const int nwg = 32 * hp_grid_b(g).per_channel();
+  const SgdRule rule = hm == nullptr ? SgdRule{}
+                                     : SgdRule::make(lr, hm->wd, hm->momentum, hm->dampening, hm->nesterov ? 1 : 0,
+                                                     hm->first_step ? 1 : 0);
+  float* mbuf = hm != nullptr ? hm->buf : nullptr;
   hp_pick<HP_MAXB>(B - 1, [&](auto nb) {
-    hp_pick<3>(mode, [&](auto md) {
+    hp_pick<4>(hm != nullptr ? 3 : mode, [&](auto md) {
       constexpr int NB = decltype(nb)::value + 1, MODE = decltype(md)::value;
       hipLaunchKernelGGL((head_upd_pb_kernel<NB, MODE>), dim3(nwg), dim3(HP_THREADS), 0, st, ya_all, ya_rs, rec, nranks,
-                         dl, W, out, g, NC, scale, lr);
+                         dl, W, out, g, NC, scale, lr, mbuf, rule);
     });
   });
   TDS_LAUNCH_CHECK();

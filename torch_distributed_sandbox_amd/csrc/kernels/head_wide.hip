@@ -506,6 +506,13 @@ __global__ __launch_bounds__(HW_THREADS) void head_wide_bwd_kernel(
 //                                                         by the one lane that owns it)
 //   MODE 1: out = scale * sum_m dl[m] (x) X_m
 //   MODE 2: out += scale * sum_m dl[m] (x) X_m
+//   MODE 3: W, mbuf = torch's SGD rule on d = scale * sum_m dl[m] (x) X_m, both in place (out = W; common.h
+//           sgd_rule_step on the value MODE 1 stores; no dW is written).  The buffer tile is loaded at the
+//           old weight's turn and address and stored beside it; a creating step (rule.first) loads none.
+//           The rule must see the whole sum once: a single launch (<= 4 * HWU_STEPS images).  Buffer and
+//           rule are one trailing argument (HWURule) that only this mode's instantiations have -- an
+//           argument the other modes merely ignored would still grow their kernel-argument segment and
+//           with it change how their scalar argument loads are merged.
 // One product per class tile: M = classes, N = 16 pooled columns, K = the image list, four images per
 // MFMA step -- the backward's dW product with its lane ownership: lane (g, n) owns columns
 // px = p0 + 4 n .. + 3, in K step s it forms X of image 4 s + g there (B operand, element e) and D
@@ -526,12 +533,19 @@ __global__ __launch_bounds__(HW_THREADS) void head_wide_bwd_kernel(
 // forms bitwise the same step.
 constexpr int HWU_STEPS = 32;
 
-template <int NT, int MODE>
+struct HWURule {
+  float* mbuf;
+  SgdRule rule;
+};
+
+template <int NT, int MODE, class... RULE>  // RULE: HWURule in MODE 3, nothing otherwise
 __global__ __launch_bounds__(HW_THREADS) void head_wide_upd_kernel(const unsigned short* __restrict__ ya,
                                                                    const float* __restrict__ rec,
                                                                    const float* __restrict__ dl, const float* W,
                                                                    float* out, PBGeom g, int B, int m0, int M, int NC,
-                                                                   int nband, int bandrows, float scale, float lr) {
+                                                                   int nband, int bandrows, float scale, float lr,
+                                                                   RULE... rule_arg) {
+  static_assert(sizeof...(RULE) == (MODE == 3 ? 1 : 0), "the rule argument belongs to MODE 3");
   __shared__ float dls[HWU_STEPS * NT * 64];
   __shared__ float2 cst[HWU_STEPS * 4];
   const int c = (int)blockIdx.x / nband, band = (int)blockIdx.x - c * nband;
@@ -555,7 +569,7 @@ __global__ __launch_bounds__(HW_THREADS) void head_wide_upd_kernel(const unsigne
   __syncthreads();
   const int Q = g.Q;
   const int64_t QQ = (int64_t)Q * Q, plane = g.plane(), cls = 32 * QQ;
-  const float* src = MODE == 0 ? W : out;  // the old values (MODE 1: none)
+  const float* src = (MODE == 0 || MODE == 3) ? W : out;  // the old values (MODE 1: none)
   const int R1 = min(g.Q4, (band + 1) * bandrows);
   for (int R = band * bandrows; R < R1; ++R) {
     const int py = 4 * R + wv;
@@ -614,6 +628,16 @@ __global__ __launch_bounds__(HW_THREADS) void head_wide_upd_kernel(const unsigne
             old[r] = full ? hw_ld4<true>(row, px, Q) : hw_ld4<false>(row, px, Q);
           }
         }
+        [[maybe_unused]] float4 mb[4];
+        if constexpr (MODE == 3) {
+          const HWURule& mr = (rule_arg, ...);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float* row = mr.mbuf + (int64_t)min(16 * t + 4 * gq + r, NC - 1) * tcls + rowoff;
+            mb[r] = mr.rule.first ? make_float4(0.f, 0.f, 0.f, 0.f)
+                                  : full ? hw_ld4<true>(row, px, Q) : hw_ld4<false>(row, px, Q);
+          }
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int j = 16 * t + 4 * gq + r;
@@ -626,6 +650,16 @@ __global__ __launch_bounds__(HW_THREADS) void head_wide_upd_kernel(const unsigne
               hw_st4(p, al, nvalid, make_float4(o.x - lr * d.x, o.y - lr * d.y, o.z - lr * d.z, o.w - lr * d.w));
             } else if constexpr (MODE == 1) {
               hw_st4(p, al, nvalid, d);
+            } else if constexpr (MODE == 3) {  // torch SGD with momentum / weight decay
+              const HWURule& mr = (rule_arg, ...);
+              const float4 o = old[r], bo = mb[r];
+              float4 bn, wn;
+              wn.x = sgd_rule_step(o.x, d.x, bo.x, mr.rule, true, bn.x);
+              wn.y = sgd_rule_step(o.y, d.y, bo.y, mr.rule, true, bn.y);
+              wn.z = sgd_rule_step(o.z, d.z, bo.z, mr.rule, true, bn.z);
+              wn.w = sgd_rule_step(o.w, d.w, bo.w, mr.rule, true, bn.w);
+              hw_st4(mr.mbuf + (int64_t)j * tcls + rowoff + px, al, nvalid, bn);
+              hw_st4(p, al, nvalid, wn);
             } else {
               const float4 o = old[r];
               hw_st4(p, al, nvalid, make_float4(o.x + d.x, o.y + d.y, o.z + d.z, o.w + d.w));
@@ -717,19 +751,30 @@ int tds_head_wide_bwd(const unsigned short* ya, TdsYaDec yd, const float* Wfc, c
 }
 
 int tds_head_wide_upd(const unsigned short* ya_all, const float* rec, int nranks, const float* dl, const float* W,
-                      float* out, int B, int Q, int NC, float scale, float lr, int mode, hipStream_t st) {
+                      float* out, int B, int Q, int NC, float scale, float lr, int mode, hipStream_t st,
+                      const TdsHeadMom* hm) {
   if (!hw_dims_ok(B, Q, NC) || nranks < 1 || nranks > (1 << 20) || mode < 0 || mode > 2) return -1;
   const PBGeom g = pb_geom(Q);
   const int nband = tds_head_bwd_pb_nblk(Q), bandrows = (g.Q4 + nband - 1) / nband;
   const int Mall = nranks * B;
+  // the rule form: mode 0's in-place step with its buffer, in the one launch that holds the whole sum
+  if (hm != nullptr && (hm->buf == nullptr || mode != 0 || out != W || !(lr > 0.f) || Mall > 4 * HWU_STEPS)) return -2;
+  const HWURule rule{hm != nullptr ? hm->buf : nullptr,
+                     hm == nullptr ? SgdRule{}
+                                   : SgdRule::make(lr, hm->wd, hm->momentum, hm->dampening, hm->nesterov ? 1 : 0,
+                                                   hm->first_step ? 1 : 0)};
   for (int m0 = 0; m0 < Mall; m0 += 4 * HWU_STEPS) {
     // image chunks after the first go on from what the one before wrote: the stepped weight, or += into dW
     const int M = min(4 * HWU_STEPS, Mall - m0), md = m0 == 0 ? mode : (mode == 0 ? 0 : 2);
     const float* Wsrc = m0 == 0 ? W : out;
     auto launch = [&](auto nt, auto mdc) {
-      hipLaunchKernelGGL((head_wide_upd_kernel<decltype(nt)::value, decltype(mdc)::value>), dim3(32 * nband),
-                         dim3(HW_THREADS), 0, st, ya_all, rec, dl, Wsrc, out, g, B, m0, M, NC, nband, bandrows, scale,
-                         lr);
+      constexpr int NT = decltype(nt)::value, MODE = decltype(mdc)::value;
+      if constexpr (MODE == 3)
+        hipLaunchKernelGGL((head_wide_upd_kernel<NT, MODE, HWURule>), dim3(32 * nband), dim3(HW_THREADS), 0, st, ya_all,
+                           rec, dl, Wsrc, out, g, B, m0, M, NC, nband, bandrows, scale, lr, rule);
+      else
+        hipLaunchKernelGGL((head_wide_upd_kernel<NT, MODE>), dim3(32 * nband), dim3(HW_THREADS), 0, st, ya_all, rec, dl,
+                           Wsrc, out, g, B, m0, M, NC, nband, bandrows, scale, lr);
     };
     auto pick = [&](auto mdc) {
       switch ((NC + 15) / 16) {
@@ -739,7 +784,8 @@ int tds_head_wide_upd(const unsigned short* ya_all, const float* rec, int nranks
         default: launch(std::integral_constant<int, 4>{}, mdc); break;
       }
     };
-    if (md == 0) pick(std::integral_constant<int, 0>{});
+    if (hm != nullptr) pick(std::integral_constant<int, 3>{});
+    else if (md == 0) pick(std::integral_constant<int, 0>{});
     else if (md == 1) pick(std::integral_constant<int, 1>{});
     else pick(std::integral_constant<int, 2>{});
     TDS_LAUNCH_CHECK();

@@ -243,9 +243,12 @@ int tds_head_bwd_pb_npass(int B);
 // The activation exchange's fc step from the all-gathered pooled inputs (head_pb.hip head_upd_pb_kernel):
 // ya_all [nranks][B][32][PB] fp16 (ya_rs elements per rank), rec [nranks][128] (tds_head_pooled_record),
 // dl [nranks * B][NC]; mode 0: out = W - lr * scale * dl^T X (out may be W), 1: out = scale * dl^T X,
-// 2: out += scale * dl^T X
+// 2: out += scale * dl^T X.  hm (mode 0, out = W; TdsHeadMom below): the rule form -- torch's SGD with
+// momentum / weight decay on d = scale * dl^T X, W and hm->buf stepped in place; -2 where it cannot run
+struct TdsHeadMom;
 int tds_head_upd_pb(const unsigned short* ya_all, int64_t ya_rs, const float* rec, int nranks, const float* dl,
-                    const float* W, float* out, int B, int Q, int NC, float scale, float lr, int mode, hipStream_t st);
+                    const float* W, float* out, int B, int Q, int NC, float scale, float lr, int mode, hipStream_t st,
+                    const TdsHeadMom* hm = nullptr);
 // The shard form (the column-sharded exchange from the pooled input): the columns of channels [c0, c1)
 // only, from ya_sh [nranks][B][c1-c0][PB] fp16 (every rank's planes of those channels); W and out
 // stay full width, nothing outside those columns is read or written.  Bitwise the columns
@@ -300,9 +303,11 @@ int tds_head_wide_bwd(const unsigned short* ya, TdsYaDec yd, const float* Wfc, c
                       float* dW, float* Wupd, int B, int Q, int NC, float scale, float lr, hipStream_t st,
                       const TdsHeadBwdFin* hf = nullptr, const TdsHeadMom* hm = nullptr);
 // tds_head_upd_pb for 11 .. 64 classes and <= 16 images per rank (head_wide_upd_kernel, fp32 MFMA):
-// ya_all [nranks][B][32][PB] fp16 contiguous, rec / dl / W / out / mode as there
+// ya_all [nranks][B][32][PB] fp16 contiguous, rec / dl / W / out / mode / hm as there.  The rule form is
+// a single launch: nranks * B > 128 images returns -2 and launches nothing
 int tds_head_wide_upd(const unsigned short* ya_all, const float* rec, int nranks, const float* dl, const float* W,
-                      float* out, int B, int Q, int NC, float scale, float lr, int mode, hipStream_t st);
+                      float* out, int B, int Q, int NC, float scale, float lr, int mode, hipStream_t st,
+                      const TdsHeadMom* hm = nullptr);
 
 // ---- zs_exchange.hip (zero-suppressed fc-input rows, parallel/zs.py)
 int64_t tds_zs_npages(int64_t n);

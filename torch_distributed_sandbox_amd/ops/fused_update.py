@@ -18,7 +18,11 @@ to ``param.grad`` (the DDP bucket).
 
 Momentum, dampening, weight decay, nesterov: the head backward's momentum form applies torch's
 whole rule and steps the parameter's momentum buffer in place (:func:`take_step`; kernels/head_pb.hip
-MOM).  The exchanges' in-place step stays plain-SGD only (:func:`take`).
+MOM).  The pooled activation exchange does the same in its update kernels at any world size
+(``take_step(param, exchanged=True)``; ``ops.head_update_pooled_step``, kernels/head_pb.hip and
+head_wide.hip MODE 3) when the step carries a momentum buffer.  Every other exchanged source (rows,
+groups, the sharded paths) and a weight-decay-only group keep the plain-SGD query (:func:`take`):
+with momentum they write the gradient and the optimizer applies the step.
 """
 from __future__ import annotations
 
@@ -27,8 +31,8 @@ _ATTR = "_tds_fused_update"
 
 def register(param, provider) -> None:
     """``provider("query")`` returns the learning rate to apply now (or None);
-    ``provider("query_step")`` the whole step (:func:`take_step`; a provider that does not know
-    the query returns None); ``provider("applied")`` records that the backward applied it."""
+    ``provider("query_step")`` / ``provider("query_exchange_step")`` the whole step
+    (:func:`take_step`; a provider that does not know the query returns None); ``provider("applied")`` records that the backward applied it."""
     setattr(param, _ATTR, provider)
 
 
@@ -52,20 +56,24 @@ def take(param, exchanged: bool = False):
     return fn("query_exchange" if exchanged else "query")
 
 
-def take_step(param):
-    """The whole step for an in-backward update of ``param`` by the kernel that produces the LOCAL
-    gradient (world size 1), or None: a dict with ``lr``, ``momentum``, ``dampening``,
-    ``weight_decay``, ``nesterov``, ``buf`` (the parameter's momentum buffer, updated in place by
-    the kernel; None without momentum) and ``first_step`` (this step creates the buffer, its
-    contents are to be ignored).  :func:`take` stays the plain-SGD query: a group with momentum or
-    weight decay answers it with None, so the exchanged paths (parallel/factored.py) keep writing
-    the gradient and the optimizer applies the step."""
+def take_step(param, exchanged: bool = False):
+    """The whole step for an in-backward update of ``param``, or None: a dict with ``lr``,
+    ``momentum``, ``dampening``, ``weight_decay``, ``nesterov``, ``buf`` (the parameter's momentum
+    buffer, updated in place by the kernel; None without momentum) and ``first_step`` (this step
+    creates the buffer, its contents are to be ignored).
+
+    ``exchanged=False``: asked by the kernel that produces the LOCAL gradient (world size 1).
+    ``exchanged=True``: asked by the pooled activation exchange (parallel/factored.py) at any world
+    size; answered only when the step carries a buffer (momentum != 0).  The dict is the step as it
+    is at query time: an update deferred past ``optimizer.step()`` keeps its ``first_step``.
+    :func:`take` stays the plain-SGD query: a group with momentum or weight decay answers it with
+    None."""
     if param is None:
         return None
     fn = getattr(param, _ATTR, None)
     if fn is None:
         return None
-    return fn("query_step")
+    return fn("query_exchange_step" if exchanged else "query_step")
 
 
 def keep_grad(param) -> bool:

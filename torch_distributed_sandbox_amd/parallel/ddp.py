@@ -624,15 +624,19 @@ class DistributedDataParallel(nn.Module):
                         return None
                     # only a plain synchronised step whose gradient lands straight in the bucket;
                     # a local gradient ("query") only at world size 1, the exchange's averaged one
-                    # ("query_exchange", parallel/factored.py) at any world size
-                    if what not in ("query", "query_exchange", "query_step"):
+                    # ("query_exchange" / "query_exchange_step", parallel/factored.py) at any world size
+                    if what not in ("query", "query_exchange", "query_step", "query_exchange_step"):
                         return None
                     if what in ("query", "query_step") and self.world_size != 1:
                         return None
-                    if what == "query_exchange" and self.keep_fused_grads:
+                    if what in ("query_exchange", "query_exchange_step") and self.keep_fused_grads:
                         return None
                     if not self.require_backward_grad_sync or p.grad is not None or id(p) in self._fused_done:
                         return None
+                    if what == "query_exchange_step":
+                        # the exchange's rule form streams a momentum buffer: only a step that has one
+                        step = optimizer.fused_step(p) if hasattr(optimizer, "fused_step") else None
+                        return step if step is not None and step["buf"] is not None else None
                     if what == "query_step":
                         # the whole step, momentum and weight decay included (one group, no maximize:
                         # the optimizer checks); a weight-decay-only group has no buffer for the

@@ -634,15 +634,21 @@ class ActivationExchange:
         st.w_ya = tdist.sendrecv(sends, recvs, group=self.group, async_op=True)
         self._start(st)
 
-    def _pooled_update(self, st: _Step, dy_all, out, scale: float, lr: float, acc: bool = False):
+    def _pooled_update(self, st: _Step, dy_all, out, scale: float, lr, acc: bool = False):
         """The fc step from the gathered pooled inputs on the current stream, after both gathers:
-        lr > 0: the weight itself, W -= lr·scale·dy_allᵀX; else ``out`` (=/+=) scale·dy_allᵀX.
+        lr > 0: the weight itself, W -= lr·scale·dy_allᵀX; ``lr`` a step dict (``_rule_step``): the
+        weight and its momentum buffer by torch's whole rule; else ``out`` (=/+=) scale·dy_allᵀX.
         Pooled shards: the columns of this rank's channels only."""
         from .. import _ext
         from . import distributed as tdist
 
         st.w_rec.wait()
         st.w_ya.wait()
+        if isinstance(lr, dict):
+            _ext.ops().head_update_pooled_step(dy_all, st.ya_all, st.rec_all, self.weight.data, lr["buf"], st.P, scale,
+                                               lr["lr"], lr["weight_decay"], lr["momentum"], lr["dampening"],
+                                               lr["nesterov"], lr["first_step"])
+            return
         mode = 0 if lr else (2 if acc else 1)
         args = (dy_all, st.ya_all, st.rec_all, self.weight.data, None if lr else out, st.P)
         if st.source == "pooled":
@@ -1004,7 +1010,7 @@ class ActivationExchange:
             return False
         if os.environ.get("TDS_EXCHANGE_UPDATE", "inline").strip().lower() != "inline":
             return False
-        lr = fused_update.take(self.weight, exchanged=True)
+        lr = fused_update.take(self.weight, exchanged=True) or self._rule_step(st)
         if not lr:
             return False
         dy = st.dy
@@ -1016,7 +1022,8 @@ class ActivationExchange:
         with torch.cuda.stream(side), torch.no_grad():
             dy.record_stream(side)
             self._gather_dy(dy, dy_all)
-            (_, _), (db, acc_b) = self._targets()
+            # (the weight steps in place: its bucket slot is not requested, so it is never allocated)
+            (_, _), (db, acc_b) = self._targets(weight=False)
             if db is not None:
                 _form_db(db, dy_all, scale, acc_b)
                 self.bias.grad = db
@@ -1024,10 +1031,28 @@ class ActivationExchange:
             ev_dy.record(side)
         self.side_pending = True  # (db was written on the side stream)
         # the update takes the record with it: _done() only drops the exchange's hold on it
-        param_fence.defer(self.weight, _DeferredUpdate(self, st, dy_all, ev_dy, scale, float(lr)))
+        param_fence.defer(self.weight, _DeferredUpdate(self, st, dy_all, ev_dy, scale,
+                                                       lr if isinstance(lr, dict) else float(lr)))
         fused_update.applied(self.weight)
         self._done()
         return True
+
+    def _rule_step(self, st: _Step):
+        """The whole optimizer step (momentum, weight decay, nesterov: ``fused_update.take_step``) for
+        the pooled update kernels' rule form, asked where the plain-SGD query declined: the activation
+        path from the pooled input only, and for a wide layer (more than ten rows) only when one launch
+        holds every rank's images (W·B <= 128: the rule must see the complete sum once).  The dict is
+        the step at query time -- lr, hyper-parameters, the buffer view and ``first_step`` -- so an
+        update deferred past ``optimizer.step()`` still creates the buffer it was asked to create.
+        None: the step keeps writing dW."""
+        from ..ops import fused_update
+
+        if st.source != "pooled" or st.path != "activations" or not st.dy.is_cuda:
+            return None
+        if self.weight.shape[0] > 10 and self.world * st.dy.shape[0] > 128:
+            return None
+        step = fused_update.take_step(self.weight, exchanged=True)
+        return step if step is not None and step["lr"] > 0.0 else None
 
     def _targets(self, weight: bool = True):
         """(dW, accumulate_w), (db, accumulate_b) — gradients accumulated under no_sync()
@@ -1073,7 +1098,8 @@ class ActivationExchange:
     def _finish(self):
         """The finish of an exchanged step, on the current stream (CPU: the end-of-backward
         callback; GPU: ``_finish_on_side``): the averaged dW / db into the bucket slots, or -- the
-        optimizer-in-backward of DDP's overlap_optimizer with plain SGD (ops/fused_update.py) -- the
+        optimizer-in-backward of DDP's overlap_optimizer with plain SGD, or from the pooled source
+        with momentum as well (``_rule_step``; ops/fused_update.py) -- the
         update-only step: the averaged step is applied to the weight while its gradient is formed,
         no dW in HBM and no separate SGD sweep over the 720 MB weight, ``.grad`` stays None; the
         bias keeps its gradient path (tiny, stepped by the optimizer)."""
@@ -1090,6 +1116,8 @@ class ActivationExchange:
         # 2. the fused learning rate, if the optimizer offers one
         lr = fused_update.take(self.weight, exchanged=True) if st.dy.is_cuda else None
         lr = float(lr) if lr else 0.0
+        if not lr:  # (the pooled source's rule form: the whole step as a dict, momentum included)
+            lr = self._rule_step(st) or 0.0
         with torch.no_grad():
             # 3. the targets: the weight itself (the bucket slot is not requested, so the update-only
             # step never allocates it), or the bucket slots
@@ -1145,7 +1173,8 @@ class _DeferredUpdate:
     columns.  (Applying the update inside the head forward while it streams the weight measured
     even with this separate sweep, 0.585 vs 0.570 ms, r5_s8.)"""
 
-    def __init__(self, ex: ActivationExchange, st: _Step, dy_all: torch.Tensor, ev_dy, scale: float, lr: float):
+    def __init__(self, ex: ActivationExchange, st: _Step, dy_all: torch.Tensor, ev_dy, scale: float, lr):
+        # (lr: the learning rate, or -- the pooled source -- the whole step captured at query time)
         self.ex, self.st, self.dy_all, self.ev_dy, self.scale, self.lr = ex, st, dy_all, ev_dy, scale, lr
         self.fused_kind = "groups" if st.source == "groups" else None
         self.next = 0  # the next group to queue (other sources: 1 once the update is queued)
