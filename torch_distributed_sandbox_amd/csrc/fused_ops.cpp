@@ -832,6 +832,126 @@ void head_update_pooled_shard(const Tensor& dl_all, const Tensor& ya_sh, const T
   head_update("head_update_pooled_shard", true, dl_all, ya_sh, rec_all, wfc, out, P, c0, c1, scale, lr, mode);
 }
 
+// The "pooled-masked" source (parallel/pooled_masked.py: format and torch reference; kernels/head_pb.hip
+// "sign-masked ya"): a rank sends the ya values whose X = relu(a ya + b) is not +0, a bit per position
+// and a value offset per page of 1024 positions; the update ops below form from every rank's payload
+// what head_update_pooled / head_update_pooled_step form from the dense ya, bit for bit.
+bool disjoint(const Tensor& a, const Tensor& b) {
+  const char* a0 = static_cast<const char*>(a.data_ptr());
+  const char* b0 = static_cast<const char*>(b.data_ptr());
+  return a0 + a.nbytes() <= b0 || b0 + b.nbytes() <= a0;
+}
+
+int64_t head_pooled_masked_pages(int64_t B, int64_t P) {
+  TORCH_CHECK(B >= 1 && P / 2 >= 4, "head_pooled_masked_pages: needs B >= 1 and P/2 >= 4 pooled columns");
+  return tds_head_pbm_npages((int)B, (int)(P / 2));
+}
+
+// ya [B, 32, PB] fp16 and the rank's record -> meta_out [pages * 33] int32, values_out [cap] fp16 (kept
+// values past cap are dropped, never written); returns the true kept count (0-d int64, no host sync)
+Tensor head_pooled_encode(const Tensor& ya, const Tensor& rec, int64_t P, const Tensor& meta_out,
+                          const Tensor& values_out) {
+  const char* who = "head_pooled_encode";
+  const int64_t Q = P / 2;
+  TORCH_CHECK(ya.dim() == 3 && ya.size(1) == 32 && ya.size(0) >= 1 && Q >= 4, who,
+              ": ya must be [B,32,PB] with P/2 >= 4 pooled columns");
+  const int64_t B = ya.size(0);
+  need(ya, at::kHalf, {B, 32, pb_plane(P)}, "ya");
+  need(rec, at::kFloat, {128}, "rec");
+  need(meta_out, at::kInt, {head_pooled_masked_pages(B, P) * 33}, "meta_out");
+  TORCH_CHECK(values_out.dim() == 1 && values_out.numel() >= 1, who, ": values_out must be 1-d with >= 1 element");
+  need(values_out, at::kHalf, {values_out.numel()}, "values_out");
+  TORCH_CHECK(ya.device() == rec.device() && ya.device() == meta_out.device() && ya.device() == values_out.device(),
+              who, ": one device");
+  TORCH_CHECK(ya.numel() < ((int64_t)1 << 31), who, ": the format's int32 offsets need < 2^31 values");
+  TORCH_CHECK(disjoint(ya, meta_out) && disjoint(ya, values_out) && disjoint(meta_out, values_out) &&
+                  disjoint(rec, meta_out) && disjoint(rec, values_out),
+              who, ": the outputs alias an input or each other");
+  c10::DeviceGuard guard(ya.device());
+  auto nnz = at::empty({}, ya.options().dtype(at::kLong));
+  auto counts = at::empty({head_pooled_masked_pages(B, P)}, ya.options().dtype(at::kInt));  // per page, between the passes
+  const int rc = tds_head_pbm_encode(ya_out(ya), rec.data_ptr<float>(), (int)B, (int)Q, meta_out.data_ptr<int>(),
+                                     counts.data_ptr<int>(), ya_out(values_out), values_out.numel(),
+                                     nnz.data_ptr<int64_t>(), stream_of(ya));
+  TORCH_CHECK(rc == 0, who, ": unsupported shape");
+  check_launches(who);
+  return nnz;
+}
+
+// both masked updates: meta_all [W, >= pages * 33] int32 (the gathered records may carry a tail),
+// values_all [W, cap] fp16, B = dl_all's rows / W images per rank
+void head_update_masked(const char* who, const Tensor& dl_all, const Tensor& meta_all, const Tensor& values_all,
+                        const Tensor& rec_all, const Tensor& wfc, const c10::optional<Tensor>& out, int64_t P,
+                        double scale, double lr, int64_t mode, const TdsHeadMom* hm = nullptr) {
+  const int64_t Q = P / 2;
+  TORCH_CHECK(wfc.defined() && wfc.is_cuda() && wfc.dim() == 2 && Q >= 4 && wfc.size(1) == 32 * Q * Q &&
+                  wfc.size(0) >= 1 && wfc.size(0) <= 10,
+              who, ": fc.weight must be a GPU tensor [<=10, 32*Q*Q] with P/2 >= 4 pooled columns");
+  const int64_t NC = wfc.size(0);
+  need(wfc, at::kFloat, {NC, 32 * Q * Q}, "fc.weight");
+  TORCH_CHECK(meta_all.dim() == 2 && values_all.dim() == 2 && meta_all.size(0) >= 1 && dl_all.dim() == 2, who,
+              ": meta_all [W,R], values_all [W,cap] and dl_all [W*B,NC]");
+  const int64_t Wr = meta_all.size(0);
+  TORCH_CHECK(dl_all.size(0) % Wr == 0 && dl_all.size(0) / Wr >= 1 && dl_all.size(0) / Wr <= 8, who,
+              ": dl_all must hold 1 .. 8 rows per rank");
+  const int64_t B = dl_all.size(0) / Wr;
+  TORCH_CHECK(meta_all.size(1) >= head_pooled_masked_pages(B, P) * 33, who, ": meta_all rows are shorter than ",
+              head_pooled_masked_pages(B, P) * 33, " words");
+  need(meta_all, at::kInt, {Wr, meta_all.size(1)}, "meta_all");
+  TORCH_CHECK(values_all.size(1) >= 1, who, ": values_all needs a capacity >= 1");
+  need(values_all, at::kHalf, {Wr, values_all.size(1)}, "values_all");
+  need(rec_all, at::kFloat, {Wr, 128}, "rec_all");
+  need(dl_all, at::kFloat, {Wr * B, NC}, "dl_all");
+  TORCH_CHECK(mode >= 0 && mode <= 2, who, ": mode 0 (update), 1 (=) or 2 (+=)");
+  float* o = wfc.data_ptr<float>();
+  if (mode != 0) {
+    TORCH_CHECK(out.has_value() && out->defined(), who, ": modes 1 and 2 write into out");
+    need(*out, at::kFloat, {NC, 32 * Q * Q}, "out (dW)");
+    o = out->data_ptr<float>();
+  } else {
+    TORCH_CHECK(lr > 0.0, who, ": mode 0 needs lr > 0");
+  }
+  const Tensor& written = mode != 0 ? *out : wfc;
+  for (const Tensor* t : {&meta_all, &values_all, &rec_all, &dl_all}) {
+    TORCH_CHECK(t->device() == wfc.device(), who, ": every tensor must be on fc.weight's device");
+    TORCH_CHECK(disjoint(*t, written), who, ": the written tensor aliases an input");
+  }
+  TORCH_CHECK(written.device() == wfc.device(), who, ": out is on another device than fc.weight");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(o) % 16 == 0 && reinterpret_cast<uintptr_t>(wfc.data_ptr()) % 16 == 0, who,
+              ": fc.weight and out must be 16-B aligned");
+  c10::DeviceGuard guard(wfc.device());
+  const int rc = tds_head_upd_pbm(meta_all.data_ptr<int>(), meta_all.size(1), ya_out(values_all), values_all.size(1),
+                                  rec_all.data_ptr<float>(), (int)Wr, dl_all.data_ptr<float>(), wfc.data_ptr<float>(),
+                                  o, (int)B, (int)Q, (int)NC, (float)scale, (float)lr, (int)mode, stream_of(wfc), hm);
+  TORCH_CHECK(rc == 0, who, ": unsupported shape");
+  check_launches(who);
+}
+
+void head_update_pooled_masked(const Tensor& dl_all, const Tensor& meta_all, const Tensor& values_all,
+                               const Tensor& rec_all, const Tensor& wfc, const c10::optional<Tensor>& out, int64_t P,
+                               double scale, double lr, int64_t mode) {
+  head_update_masked("head_update_pooled_masked", dl_all, meta_all, values_all, rec_all, wfc, out, P, scale, lr, mode);
+}
+
+// head_update_pooled_step from the masked payloads: the same checks of the buffer, the same rule
+void head_update_pooled_masked_step(const Tensor& dl_all, const Tensor& meta_all, const Tensor& values_all,
+                                    const Tensor& rec_all, const Tensor& wfc, const Tensor& mbuf, int64_t P,
+                                    double scale, double lr, double weight_decay, double momentum, double dampening,
+                                    bool nesterov, bool first_step) {
+  const char* who = "head_update_pooled_masked_step";
+  TORCH_CHECK(wfc.defined() && wfc.is_cuda(), who, ": fc.weight must be a GPU tensor");
+  need(mbuf, at::kFloat, wfc.sizes().vec(), "mbuf");
+  TORCH_CHECK(mbuf.device() == wfc.device(), who, ": mbuf is on another device than fc.weight");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(mbuf.data_ptr()) % 16 == 0, who, ": mbuf must be 16-B aligned");
+  TORCH_CHECK(disjoint(mbuf, wfc), who, ": mbuf aliases fc.weight");
+  for (const Tensor* t : {&meta_all, &values_all, &rec_all, &dl_all})
+    TORCH_CHECK(t->defined() && t->is_cuda() && disjoint(*t, mbuf), who, ": mbuf aliases an input");
+  TORCH_CHECK(momentum != 0.0, who, ": needs momentum != 0 (head_update_pooled_masked mode 0 is the plain step)");
+  const TdsHeadMom hm{mbuf.data_ptr<float>(), (float)weight_decay, (float)momentum, (float)dampening, nesterov,
+                      first_step};
+  head_update_masked(who, dl_all, meta_all, values_all, rec_all, wfc, c10::nullopt, P, scale, lr, 0, &hm);
+}
+
 // BN2 partial-sum workspace (doubles) of the head backward for B images at pooled size P/2: the BN2
 // partials [32][npass * nblk][4] (fp32 dz / stored dz sums), then 16 doubles = g2m's 32 per-channel
 // scales 2^-e_c (fp32) for the K-chunked launches (the finalizing call copies them into kbuf[96..128))
@@ -1618,6 +1738,18 @@ TORCH_LIBRARY_FRAGMENT(tdsa, m) {
       "head_update_pooled_shard(Tensor dl_all, Tensor ya_sh, Tensor rec_all, Tensor(a!) wfc, Tensor(b!)? out, int P, "
       "int c0, int c1, float scale, float lr, int mode) -> ()",
       &head_update_pooled_shard);
+  m.def("head_pooled_masked_pages(int B, int P) -> int", &head_pooled_masked_pages);
+  m.def("head_pooled_encode(Tensor ya, Tensor rec, int P, Tensor(a!) meta_out, Tensor(b!) values_out) -> Tensor",
+        &head_pooled_encode);
+  m.def(
+      "head_update_pooled_masked(Tensor dl_all, Tensor meta_all, Tensor values_all, Tensor rec_all, Tensor(a!) wfc, "
+      "Tensor(b!)? out, int P, float scale, float lr, int mode) -> ()",
+      &head_update_pooled_masked);
+  m.def(
+      "head_update_pooled_masked_step(Tensor dl_all, Tensor meta_all, Tensor values_all, Tensor rec_all, "
+      "Tensor(a!) wfc, Tensor(b!) mbuf, int P, float scale, float lr, float weight_decay, float momentum, "
+      "float dampening, bool nesterov, bool first_step) -> ()",
+      &head_update_pooled_masked_step);
   m.def("mag_numel(int B, int P) -> int", &mag_numel);
   m.def("mag_ypart_count() -> int", &mag_ypart_count);
   m.def("conv2_bwd_clock_dump(int nwg) -> Tensor", &conv2_bwd_clock_dump);

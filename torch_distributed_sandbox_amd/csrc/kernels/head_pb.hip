@@ -923,6 +923,293 @@ __global__ __launch_bounds__(HP_REC) void hp_record_kernel(const float* __restri
   rec[t] = v;
 }
 
+// ---------------------------------------------------------------------------- sign-masked ya
+// The activation exchange's "pooled-masked" source (parallel/pooled_masked.py has the format and the
+// torch reference): about half of X = relu(a ya + b) is exactly zero, and which half is known once the
+// rank's head record exists, so a rank sends only the ya values whose X is not +0 and a bit per
+// position.  A PAGE is one chunk of the head kernels' walk -- the 32 blocks (1024 values) of one
+// (image, channel, block row, chunk); the last chunk of a block row may hold fewer real blocks, the
+// missing ones count as all-dropped.  meta[p * 33] is page p's value offset (the exclusive prefix
+// sum of the kept counts in page order), meta[p * 33 + 1 + k] the mask word of block k: bit i <->
+// value i = (py % 4) * 8 + px % 8 of the block.  values holds the kept fp16 values in (page, block, i)
+// order.  A value is kept iff hp_relu(z) has any bit set, z formed by hp_fma4 from the rank's record
+// exactly as the head kernels form it, and lies inside the Q x Q image; a dropped position is +0.f
+// in X, so X rebuilt from (meta, values) is bitwise the X the dense kernels form.
+//
+// Encode: two passes over ya with a one-workgroup prefix sum of the page counts between them (no
+// cross-workgroup wait; ya's second read comes from the Infinity Cache at the bench shape, 178 of its
+// 256 MB).  The counts are scanned in a dense int32 array of their own and pass 2 puts each page's
+// offset into its record: summed in place in meta, 132 B apart, the one workgroup's strided accesses
+// took 0.30 ms for 90 K pages (0.09 ms with only the stores strided).  Both passes use the head kernels' thread mapping (HPThread), so a thread's four
+// predicates are the four it decodes in the update kernel.
+constexpr int HPM_META = 33;  // int32 per page: offset | 32 mask words
+
+__host__ __device__ inline int hpm_nch(const PBGeom& g) { return (g.Q8 + 31) / 32; }
+
+// page p of a rank's ya -> its (image, channel, block row, chunk)
+struct HPMPage {
+  int b, c, R, chunk;
+  __device__ HPMPage(int64_t p, const PBGeom& g) {
+    const int nch = hpm_nch(g);
+    chunk = (int)(p % nch);
+    p /= nch;
+    R = (int)(p % g.Q4);
+    p /= g.Q4;
+    c = (int)(p & 31);
+    b = (int)(p >> 5);
+  }
+};
+
+// this thread's 4 ya values of page pg (idle lanes of the last chunk: a valid block, never kept)
+__device__ __forceinline__ uint2 hpm_ld_ya(const unsigned short* __restrict__ ya, const PBGeom& g, const HPMPage& pg,
+                                           const HPThread& th) {
+  const int bc = th.blk < g.Q8 ? th.blk : g.Q8 - 1;
+  return *reinterpret_cast<const uint2*>(ya + (((int64_t)(pg.b * 32 + pg.c) * g.Q4 + pg.R) * g.Q8 + bc) * 32 +
+                                         th.part * 4);
+}
+
+// inclusive prefix sum over the wave's 64 lanes by DPP: shifts inside the rows of 16, then lane 15 of
+// rows 0 / 2 into rows 1 / 3 and lane 31 into rows 2 and 3 (lanes without a source add 0)
+template <int CTRL, int ROWS>
+__device__ __forceinline__ int hpm_dpp_add(int v) {
+  return v + __builtin_amdgcn_update_dpp(0, v, CTRL, ROWS, 0xf, false);
+}
+__device__ __forceinline__ int hpm_wave_iscan(int v) {
+  v = hpm_dpp_add<0x111, 0xf>(v);  // row_shr:1
+  v = hpm_dpp_add<0x112, 0xf>(v);  // row_shr:2
+  v = hpm_dpp_add<0x114, 0xf>(v);  // row_shr:4
+  v = hpm_dpp_add<0x118, 0xf>(v);  // row_shr:8
+  v = hpm_dpp_add<0x142, 0xa>(v);  // row_bcast:15
+  v = hpm_dpp_add<0x143, 0xc>(v);  // row_bcast:31
+  return v;
+}
+
+// A thread's decode of one page record mp (wave-uniform pointer) with value offset off: its four keep
+// bits (bit k <-> column px0 + k) and the index of its first kept value = the page offset + the kept
+// counts of the chunk's earlier blocks + the kept bits of its own block below its four.  Lanes 2k and 2k+1 hold block k's
+// word, so the inclusive scan of the popcounts over the 64 lanes counts every earlier block twice and
+// the own block once or twice: no LDS, no barrier, the same scan in each of the four waves.
+struct HPMPos {
+  uint32_t nib;
+  int64_t pos;
+  __device__ __forceinline__ HPMPos(const int* __restrict__ mp, int off, const HPThread& th) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t word = (uint32_t)mp[1 + (lane >> 1)];
+    const int pc = __builtin_popcount(word);
+    const int before = (hpm_wave_iscan(pc) - ((lane & 1) + 1) * pc) >> 1;
+    const int sh = th.part * 4;  // (py % 4) * 8 + 4 * half
+    nib = (word >> sh) & 0xfu;
+    pos = (int64_t)off + before + __builtin_popcount(word & ((1u << sh) - 1u));
+  }
+};
+
+// pass 1: one page per workgroup -- the mask words and the page's kept count
+__global__ __launch_bounds__(HP_THREADS) void hpm_mask_kernel(const unsigned short* __restrict__ ya,
+                                                              const float* __restrict__ rec, int* __restrict__ meta,
+                                                              int* __restrict__ counts, PBGeom g) {
+  __shared__ uint32_t words[32];
+  const int64_t p = blockIdx.x;
+  const HPMPage pg(p, g);
+  const HPThread th(pg.chunk);
+  const int lane = threadIdx.x & 63;
+  const TdsYaDec yd{rec + 68, reinterpret_cast<const uint32_t*>(rec + 64)};
+  const float a = rec[pg.c], ad = a * hp_ydec(yd.ysc), bd = fmaf(a, yd.b2[pg.c], rec[32 + pg.c]);
+  float zz[4];
+  hp_fma4(ad, hpm_ld_ya(ya, g, pg, th), bd, zz);
+  const int py = 4 * pg.R + th.prow, px0 = th.blk * 8 + th.half * 4;
+  const bool rok = th.blk < g.Q8 && py < g.Q;
+  // ballot k: bit l <-> lane l keeps its column k.  Lane l < 32 assembles block l's byte of this wave's
+  // pooled row from bits 2l (columns 0 .. 3) and 2l+1 (columns 4 .. 7) of the four ballots
+  uint32_t byte = 0u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const bool keep = rok && px0 + k < g.Q && __float_as_uint(hp_relu(zz[k])) != 0u;
+    const uint32_t pair = (uint32_t)(__builtin_amdgcn_ballot_w64(keep) >> (2 * (lane & 31))) & 3u;
+    byte |= ((pair & 1u) << k) | ((pair >> 1) << (4 + k));
+  }
+  // (byte w of word k: the bits of pooled row w -- one plain LDS byte per lane, no atomics)
+  if (lane < 32) reinterpret_cast<unsigned char*>(words)[lane * 4 + th.prow] = (unsigned char)byte;
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    const uint32_t w = words[lane & 31];
+    const int total = wave_sum(lane < 32 ? __builtin_popcount(w) : 0);
+    if (lane < 32) meta[p * HPM_META + 1 + lane] = (int)w;
+    if (lane == 0) counts[p] = total;
+  }
+}
+
+// between the passes, one workgroup: the counts become the page offsets, their exclusive prefix sums,
+// in place (a thread sums a run of consecutive counts, the runs are scanned through LDS), and the total
+__global__ __launch_bounds__(1024) void hpm_scan_kernel(int* __restrict__ counts, int64_t npages,
+                                                        int64_t* __restrict__ nnz) {
+  __shared__ int64_t part[1024];
+  const int t = threadIdx.x;
+  const int64_t per = (npages + 1023) / 1024, q0 = min(npages, t * per), q1 = min(npages, q0 + per);
+  int64_t s = 0;
+#pragma unroll 8
+  for (int64_t q = q0; q < q1; ++q) s += counts[q];
+  part[t] = s;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {
+    const int64_t o = t >= d ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += o;
+    __syncthreads();
+  }
+  int64_t run = part[t] - s;
+#pragma unroll 8
+  for (int64_t q = q0; q < q1; ++q) {
+    const int n = counts[q];
+    counts[q] = (int)run;
+    run += n;
+  }
+  if (t == 1023) *nnz = part[1023];
+}
+
+// pass 2: the page's offset into its record, a thread's kept values to their places (consecutive: a
+// block's values are in i order); what lies past the capacity is dropped
+__global__ __launch_bounds__(HP_THREADS) void hpm_compact_kernel(const unsigned short* __restrict__ ya,
+                                                                 const int* __restrict__ offs, int* __restrict__ meta,
+                                                                 unsigned short* __restrict__ vals, int64_t cap,
+                                                                 PBGeom g) {
+  const int64_t p = blockIdx.x;
+  const HPMPage pg(p, g);
+  const HPThread th(pg.chunk);
+  const uint2 y = hpm_ld_ya(ya, g, pg, th);
+  const int off = offs[p];
+  const HPMPos d(meta + p * HPM_META, off, th);
+  if (threadIdx.x == 0) meta[p * HPM_META] = off;
+  const unsigned short h[4] = {(unsigned short)y.x, (unsigned short)(y.x >> 16), (unsigned short)y.y,
+                               (unsigned short)(y.y >> 16)};
+  int64_t pos = d.pos;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if ((d.nib >> k) & 1u) {
+      if (pos >= 0 && pos < cap) vals[pos] = h[k];
+      ++pos;
+    }
+  }
+}
+
+// head_upd_pb_kernel from the masked payloads: meta_all [nranks][meta_rs] and vals_all [nranks][cap]
+// in place of ya_all.  Same grid, walk, modes and epilogue, and the same arithmetic in the same order
+// (ranks ascending, then images; hp_fma4 / hp_relu / fmaf per element) on the same values: a kept
+// value is read back where the encoder put it, a dropped one is +0.f -- the dense kernel's X there --
+// so out, W and mbuf are bitwise the dense kernel's.  Per (rank, image) a thread decodes its page record
+// (HPMPos) and loads its up to four values by 2-byte loads; every index is clamped into [0, cap) first,
+// so a short or corrupt payload gives wrong numbers, never an address outside vals_all.  The weight is
+// read by the modes that step it only.
+template <int NB, int MODE>
+__global__ __launch_bounds__(HP_THREADS) void head_upd_pbm_kernel(
+    const int* __restrict__ meta_all, int64_t meta_rs, const unsigned short* __restrict__ vals_all, int64_t cap,
+    const float* __restrict__ rec, int nranks, const float* __restrict__ dl, const float* W, float* out, PBGeom g, int NC,
+    float scale, float lr, float* mbuf, SgdRule rule) {
+  const HPGrid hg = hp_grid_b(g);
+  const int c = (int)blockIdx.x / hg.per_channel(), band = (int)blockIdx.x - c * hg.per_channel();
+  const int Q = g.Q;
+  const int nch = hpm_nch(g);
+  const int R0 = band * HP_BAND_B, nit = (min(g.Q4, R0 + HP_BAND_B) - R0) * nch;
+#pragma unroll 1
+  for (int i = 0; i < nit; ++i) {
+    const int R = R0 + i / nch, chunk = i % nch;
+    const HPThread th(chunk);
+    const HPRow rw(g, th, c, R);
+    [[maybe_unused]] float4 w[10];
+    if constexpr (MODE == 0 || MODE == 3) {
+#pragma unroll
+      for (int j = 0; j < 10; ++j) w[j] = hp_ld4(W + (int64_t)(j < NC ? j : 0) * 32 * Q * (int64_t)Q + rw.ldoff);
+    }
+    float acc[10][4];
+#pragma unroll
+    for (int j = 0; j < 10; ++j)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc[j][k] = 0.f;
+#pragma unroll 1
+    for (int r = 0; r < nranks; ++r) {
+      const int* mr = meta_all + r * meta_rs;
+      const unsigned short* vr = vals_all + r * cap;
+      uint2 y[NB];
+      uint32_t nib[NB];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        const int64_t page = (((int64_t)(b * 32 + c) * g.Q4 + R) * nch + chunk);
+        const int* mp = mr + page * HPM_META;
+        const HPMPos d(mp, mp[0], th);
+        nib[b] = d.nib;
+        uint32_t h[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int64_t at = d.pos + __builtin_popcount(d.nib & ((1u << k) - 1u));
+          h[k] = vr[min(max(at, (int64_t)0), cap - 1)];
+        }
+        y[b] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
+      }
+      // rank r's head constants, formed as its head kernels formed them (head_fwd_pb_kernel)
+      const float* rr = rec + (int64_t)r * HP_REC;
+      const TdsYaDec yd{rr + 68, reinterpret_cast<const uint32_t*>(rr + 64)};
+      const float a = rr[c], ad = a * hp_ydec(yd.ysc), bd = fmaf(a, yd.b2[c], rr[32 + c]);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        float zz[4];
+        hp_fma4(ad, y[b], bd, zz);
+        float x[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = ((nib[b] >> k) & 1u) ? hp_relu(zz[k]) : 0.f;
+#pragma unroll
+        for (int j = 0; j < 10; ++j) {
+          if (j < NC) {
+            const float dv = dl[(r * NB + b) * NC + j];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[j][k] = fmaf(dv, x[k], acc[j][k]);
+          }
+        }
+      }
+    }
+    if constexpr (MODE == 0 || MODE == 3) hp_fix_w(w, rw.sh, rw.nvalid, NC);
+    // MODE 3: the buffer's groups HP_MOM_AHEAD classes ahead, as in head_upd_pb_kernel
+    [[maybe_unused]] float4 mb[HP_MOM_AHEAD];
+    [[maybe_unused]] const int64_t cls = (int64_t)32 * Q * (int64_t)Q;
+    if constexpr (MODE == 3) {
+#pragma unroll
+      for (int j = 0; j < HP_MOM_AHEAD; ++j)
+        mb[j] = rule.first ? make_float4(0.f, 0.f, 0.f, 0.f) : hp_ld4(mbuf + (j < NC ? j : 0) * cls + rw.ldoff);
+    }
+#pragma unroll
+    for (int j = 0; j < 10; ++j) {
+      [[maybe_unused]] float4 bcur;
+      if constexpr (MODE == 3) {
+        bcur = mb[j % HP_MOM_AHEAD];
+        if (j + HP_MOM_AHEAD < 10 && !rule.first)
+          mb[j % HP_MOM_AHEAD] = hp_ld4(mbuf + (j + HP_MOM_AHEAD < NC ? j + HP_MOM_AHEAD : 0) * cls + rw.ldoff);
+      }
+      if (j < NC) {
+        const float4 d = make_float4(scale * acc[j][0], scale * acc[j][1], scale * acc[j][2], scale * acc[j][3]);
+        if constexpr (MODE == 0) {
+          const float4 wj = w[j];
+          hp_store4(out, g, rw, j, make_float4(wj.x - lr * d.x, wj.y - lr * d.y, wj.z - lr * d.z, wj.w - lr * d.w));
+        } else if constexpr (MODE == 1) {
+          hp_store4(out, g, rw, j, d);
+        } else if constexpr (MODE == 3) {
+          const float4 wj = w[j], bo = hp_fix_b(bcur, rw.sh);
+          float4 bn, wn;
+          wn.x = sgd_rule_step(wj.x, d.x, bo.x, rule, true, bn.x);
+          wn.y = sgd_rule_step(wj.y, d.y, bo.y, rule, true, bn.y);
+          wn.z = sgd_rule_step(wj.z, d.z, bo.z, rule, true, bn.z);
+          wn.w = sgd_rule_step(wj.w, d.w, bo.w, rule, true, bn.w);
+          hp_store4(mbuf, g, rw, j, bn);
+          hp_store4(out, g, rw, j, wn);
+        } else if (rw.nvalid > 0) {
+          float* p = out + (int64_t)j * 32 * Q * (int64_t)Q + rw.off;
+          const float e[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if (k < rw.nvalid) p[k] += e[k];
+        }
+      }
+    }
+  }
+}
+
 }  // namespace tds
 
 using namespace tds;
@@ -962,6 +1249,47 @@ int tds_head_upd_pb(const unsigned short* ya_all, int64_t ya_rs, const float* re
       constexpr int NB = decltype(nb)::value + 1, MODE = decltype(md)::value;
       hipLaunchKernelGGL((head_upd_pb_kernel<NB, MODE>), dim3(nwg), dim3(HP_THREADS), 0, st, ya_all, ya_rs, rec, nranks,
                          dl, W, out, g, NC, scale, lr, mbuf, rule);
+    });
+  });
+  TDS_LAUNCH_CHECK();
+  return 0;
+}
+
+int64_t tds_head_pbm_npages(int B, int Q) {
+  const PBGeom g = pb_geom(Q);
+  return (int64_t)B * 32 * g.Q4 * hpm_nch(g);
+}
+
+int tds_head_pbm_encode(const unsigned short* ya, const float* rec, int B, int Q, int* meta, int* counts,
+                        unsigned short* vals, int64_t cap, int64_t* nnz, hipStream_t st) {
+  const PBGeom g = pb_geom(Q);
+  const int64_t np = tds_head_pbm_npages(B, Q);
+  // (the offsets are int32; one workgroup per page)
+  if (B < 1 || Q < 4 || cap < 1 || (int64_t)B * 32 * g.plane() >= ((int64_t)1 << 31)) return -1;
+  hipLaunchKernelGGL(hpm_mask_kernel, dim3((unsigned)np), dim3(HP_THREADS), 0, st, ya, rec, meta, counts, g);
+  hipLaunchKernelGGL(hpm_scan_kernel, dim3(1), dim3(1024), 0, st, counts, np, nnz);
+  hipLaunchKernelGGL(hpm_compact_kernel, dim3((unsigned)np), dim3(HP_THREADS), 0, st, ya, counts, meta, vals, cap, g);
+  TDS_LAUNCH_CHECK();
+  return 0;
+}
+
+int tds_head_upd_pbm(const int* meta_all, int64_t meta_rs, const unsigned short* vals_all, int64_t cap,
+                     const float* rec, int nranks, const float* dl, const float* W, float* out, int B, int Q, int NC,
+                     float scale, float lr, int mode, hipStream_t st, const TdsHeadMom* hm) {
+  if (B < 1 || B > HP_MAXB || NC < 1 || NC > 10 || Q < 4 || nranks < 1 || mode < 0 || mode > 2) return -1;
+  if (cap < 1 || meta_rs < tds_head_pbm_npages(B, Q) * HPM_META) return -1;
+  if (hm != nullptr && (hm->buf == nullptr || mode != 0 || out != W || !(lr > 0.f))) return -2;
+  const PBGeom g = pb_geom(Q);
+  const int nwg = 32 * hp_grid_b(g).per_channel();
+  const SgdRule rule = hm == nullptr ? SgdRule{}
+                                     : SgdRule::make(lr, hm->wd, hm->momentum, hm->dampening, hm->nesterov ? 1 : 0,
+                                                     hm->first_step ? 1 : 0);
+  float* mbuf = hm != nullptr ? hm->buf : nullptr;
+  hp_pick<HP_MAXB>(B - 1, [&](auto nb) {
+    hp_pick<4>(hm != nullptr ? 3 : mode, [&](auto md) {
+      constexpr int NB = decltype(nb)::value + 1, MODE = decltype(md)::value;
+      hipLaunchKernelGGL((head_upd_pbm_kernel<NB, MODE>), dim3(nwg), dim3(HP_THREADS), 0, st, meta_all, meta_rs,
+                         vals_all, cap, rec, nranks, dl, W, out, g, NC, scale, lr, mbuf, rule);
     });
   });
   TDS_LAUNCH_CHECK();

@@ -256,6 +256,18 @@ int tds_head_upd_pb(const unsigned short* ya_all, int64_t ya_rs, const float* re
 int tds_head_upd_pb_shard(const unsigned short* ya_sh, const float* rec, int nranks, const float* dl, const float* W,
                           float* out, int B, int Q, int NC, int c0, int c1, float scale, float lr, int mode,
                           hipStream_t st);
+// The sign-masked payload of one rank's ya (head_pb.hip "sign-masked ya"; parallel/pooled_masked.py):
+// meta [npages * 33] int32, counts [npages] int32 scratch, vals [cap] fp16 (kept values past cap are
+// dropped, never written), nnz the true kept count (int64 device scalar).  rec: the rank's record.  -1: B < 1, Q < 4, cap < 1 or
+// 2^31 values and more
+int64_t tds_head_pbm_npages(int B, int Q);
+int tds_head_pbm_encode(const unsigned short* ya, const float* rec, int B, int Q, int* meta, int* counts,
+                        unsigned short* vals, int64_t cap, int64_t* nnz, hipStream_t st);
+// tds_head_upd_pb from the all-gathered masked payloads, bitwise the same result: meta_all
+// [nranks][meta_rs >= npages * 33], vals_all [nranks][cap]; every value index is clamped into [0, cap)
+int tds_head_upd_pbm(const int* meta_all, int64_t meta_rs, const unsigned short* vals_all, int64_t cap,
+                     const float* rec, int nranks, const float* dl, const float* W, float* out, int B, int Q, int NC,
+                     float scale, float lr, int mode, hipStream_t st, const TdsHeadMom* hm = nullptr);
 // a rank's record for tds_head_upd_pb: aff2 [64] | ya scale words [3] (ysc nullptr: 1, 1, 1) | 0 | b2 [32] | 0
 void tds_head_pooled_record(const float* aff2, const float* b2, const uint32_t* ysc, float* rec, hipStream_t st);
 // channels [c0, c1) only (K-chunked fc gradient: each chunk's dW columns can be all-reduced as

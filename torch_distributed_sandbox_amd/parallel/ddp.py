@@ -129,7 +129,7 @@ class DistributedDataParallel(nn.Module):
         if grad_exchange not in ("auto", "allreduce", "activations", "sharded", "chunked"):
             raise ValueError(f"grad_exchange must be auto|allreduce|activations|sharded|chunked, got {grad_exchange!r}")
         self.grad_exchange = grad_exchange
-        # the exchange's source (parallel/factored.py: pooled | rows | pooled-sharded).  A non-empty
+        # the exchange's source (parallel/factored.py: pooled | rows | pooled-sharded | pooled-masked).  A non-empty
         # TDS_EXCHANGE_SOURCE overrides the argument: the operator's switch (like
         # TDS_EXCHANGE_UPDATE), so a launcher that does not offer a value can still run it
         env_source = os.environ.get("TDS_EXCHANGE_SOURCE", "").strip()

@@ -75,6 +75,18 @@ the rows path.  The activation path under this source is the pooled one above.  
 world > 1 under DDP's overlapped optimizer (``_pooled_sharded_ok``): the sharded path then stays on
 the rows.
 
+Pooled masked source (``source="pooled-masked"``, opt-in): the pooled activation path with ya sent
+sign-masked (parallel/pooled_masked.py).  X is exactly zero wherever ``a*ya + b <= 0``, and a rank
+knows where once its head record exists, so it encodes ya right there (``ops.head_pooled_encode``:
+a bit per position, a value offset per page of 1024 positions, the kept fp16 values) and the ranks
+gather the fixed-size records with the kept count in their tail, then the values at a capacity kept
+from the earlier steps' counts -- the rows path's capacity policy and count check
+(``_begin_masked``, ``_masked_over``).  Every rank forms the step from the payloads
+(``ops.head_update_pooled_masked[_step]``), bitwise what ``head_update_pooled[_step]`` forms from
+the dense ya.  A step in which some rank kept more values than the capacity gathers ya dense at the
+consumer and runs as a plain pooled step.  A layer of more than ten rows, more than eight images
+per rank and the sharded path run as under ``"pooled"``.
+
 Column groups (activation path, zero-suppressed): the rows travel as ``groups`` column ranges
 (whole channel planes on the fused head), each encoded and gathered on its own.  The fused head
 forward runs one launch per group and hands each group's rows over as soon as its launch is
@@ -111,6 +123,7 @@ Protocol (driven by ``parallel/ddp.py``):
 """
 from __future__ import annotations
 
+import math
 import os
 
 from typing import List, Optional, Tuple
@@ -186,7 +199,9 @@ def plane_shards(world: int, planes: int = 32) -> List[Tuple[int, int]]:
 
 
 # what an exchange sends (ActivationExchange ``source``, DDP ``exchange_source``, --exchange-source)
-EXCHANGE_SOURCES = ("pooled", "rows", "pooled-sharded")
+EXCHANGE_SOURCES = ("pooled", "rows", "pooled-sharded", "pooled-masked")
+# the sources under which a layer with a fused head behind it exchanges from the pooled input
+_POOLED_SOURCES = ("pooled", "pooled-sharded", "pooled-masked")
 
 
 class _Step:
@@ -212,6 +227,7 @@ class _Step:
         # of this rank's channels), their works, the head's P and the channel shards
         self.ya = self.rec = self.ya_all = self.rec_all = self.w_ya = self.w_rec = None
         self.P, self.shards = 0, None
+        self.m = None         # pooled, sent sign-masked: the encoded exchange (``_begin_masked``)
         self.works = []       # chunked: the per-chunk all-reduce works
 
     def tensors(self) -> List[torch.Tensor]:
@@ -221,6 +237,8 @@ class _Step:
             out += [z["x_local"], z["meta_all"], z["vals_all"], z["meta"], z["vals"]]
         if self.z is not None:
             out += [self.z["meta_recv"], self.z["vals_recv"], *self.z["keep"]]
+        if self.m is not None:
+            out += [self.m["meta"], self.m["vals"], self.m["meta_all"], self.m["vals_all"]]
         return [t for t in out if t is not None]
 
 
@@ -244,7 +262,9 @@ class ActivationExchange:
             raise ValueError(f"ActivationExchange source must be {'|'.join(EXCHANGE_SOURCES)}, got {source!r}")
         # "pooled": the activation path takes the fused head's pooled input when the layer offers
         # it (begin_pooled); "rows": always the fc input rows X (begin / begin_groups);
-        # "pooled-sharded": as "pooled", and the sharded path takes the pooled input too
+        # "pooled-sharded": as "pooled", and the sharded path takes the pooled input too;
+        # "pooled-masked": as "pooled", a layer of at most ten rows sends ya sign-masked
+        # (parallel/pooled_masked.py)
         self.source = source
         # a layer of more than WIDE_ROWS rows (the fused ConvNet's wide head, up to 64 classes) runs the
         # activation path from the pooled input or nothing (``path``, ``begin``)
@@ -444,7 +464,16 @@ class ActivationExchange:
         pb = pooled_plane(in_f) if self.pooled_capable() else None
         if path == "activations" and pb is not None:
             gather("head record all-gather", 128, torch.float32)
-            gather("pooled input (ya) all-gather (fp16)", rows * 32 * pb, torch.float16)
+            if self.source == "pooled-masked" and out_f <= 10 and rows <= 8 and rows * 32 * pb < (1 << 31):
+                from . import pooled_masked as pm
+
+                cap = self._cap.get("pooled-masked")
+                gather("masked ya records all-gather (int32)",
+                       _meta_row(pm.meta_numel(rows, math.isqrt(in_f // 32))), torch.int32)
+                gather("masked ya values all-gather (fp16, first-step capacity)",
+                       min(rows * 32 * pb, cap) if cap else rows * 32 * pb, torch.float16)
+            else:
+                gather("pooled input (ya) all-gather (fp16)", rows * 32 * pb, torch.float16)
             gather("dY all-gather", rows * out_f, torch.float32)
         elif path == "activations":
             if zs_ok:
@@ -563,7 +592,7 @@ class ActivationExchange:
         "pooled-sharded", a GPU weight whose inputs are the fused head's 32 square planes)?  The byte
         model and the preflight price it so; the fused ConvNet head then takes it (a generic Linear
         still sends its rows)."""
-        return (self.source in ("pooled", "pooled-sharded") and self.weight.is_cuda
+        return (self.source in _POOLED_SOURCES and self.weight.is_cuda
                 and pooled_plane(self.weight.shape[1]) is not None)
 
     def _pooled_sharded_ok(self) -> bool:
@@ -582,7 +611,7 @@ class ActivationExchange:
         (``begin_pooled``): the activation path, or the sharded path under "pooled-sharded"?"""
         path = self._eligible(rows)
         if path == "activations":
-            return self.source in ("pooled", "pooled-sharded")
+            return self.source in _POOLED_SOURCES
         return path == "sharded" and self._pooled_sharded_ok()
 
     def begin_pooled(self, ya: torch.Tensor, rec: torch.Tensor, P: int) -> None:
@@ -598,9 +627,71 @@ class ActivationExchange:
             self._begin_pooled_sharded(ya, rec, P)
             return
         st = self._pooled_step("activations", "pooled", ya, rec, P)
-        st.ya_all = torch.empty((self.world,) + tuple(ya.shape), device=ya.device, dtype=ya.dtype)
-        st.w_ya = tdist.all_gather_into_tensor(st.ya_all.view(-1), ya.view(-1), group=self.group, async_op=True)
+        # the masked kernels stop at ten rows and eight images per rank, the format's offsets at 2^31 values
+        if (self.source == "pooled-masked" and self.weight.shape[0] <= 10 and ya.shape[0] <= 8
+                and ya.numel() < (1 << 31)):
+            self._begin_masked(st)
+        else:
+            self._gather_ya(st)
         self._start(st)
+
+    def _gather_ya(self, st: _Step, async_op: bool = True) -> None:
+        """The dense all-gather of a pooled step's ya."""
+        from . import distributed as tdist
+
+        st.ya_all = torch.empty((self.world,) + tuple(st.ya.shape), device=st.ya.device, dtype=st.ya.dtype)
+        st.w_ya = tdist.all_gather_into_tensor(st.ya_all.view(-1), st.ya.view(-1), group=self.group,
+                                               async_op=async_op)
+
+    def _begin_masked(self, st: _Step) -> None:
+        """The pooled step's ya sent sign-masked (parallel/pooled_masked.py) on the rows path's protocol
+        (``_begin_zs``): encode on the current stream, gather the fixed-size records with each rank's
+        kept count in their tail, then the values at the capacity kept from earlier steps' counts; the
+        counts go to the host behind the first gather for the consumer's check (``_masked_over``)."""
+        from . import distributed as tdist
+        from . import pooled_masked as pm
+
+        ya, dev, W = st.ya, st.ya.device, self.world
+        B, Q = ya.shape[0], st.P // 2
+        M = pm.meta_numel(B, Q)
+        R = _meta_row(M)
+        cap = max(1, self._take_cap("pooled-masked", ya.numel()))
+        meta = torch.empty(R, device=dev, dtype=torch.int32)
+        vals = torch.empty(cap, device=dev, dtype=torch.float16)
+        nnz = pm.encode(ya, st.rec, st.P, meta[:M], vals)
+        meta[R - 2:].view(torch.int64).copy_(nnz.view(1).to(dev))
+        meta_all = torch.empty(W * R, device=dev, dtype=torch.int32)
+        w_meta = tdist.all_gather_into_tensor(meta_all, meta, group=self.group, async_op=True)
+        counts_host, counts_ev = self._counts_to_host(w_meta, meta_all, lambda: _counts_of(meta_all, W, R))
+        vals_all = torch.empty(W * cap, device=dev, dtype=torch.float16)
+        w_vals = tdist.all_gather_into_tensor(vals_all, vals, group=self.group, async_op=True)
+        st.tag = "(pooled-masked)"
+        st.m = {"n": ya.numel(), "R": R, "cap": cap, "meta": meta, "vals": vals, "meta_all": meta_all,
+                "vals_all": vals_all, "w_meta": w_meta, "w_vals": w_vals, "counts_host": counts_host,
+                "counts_ev": counts_ev, "sent": pm.payload_bytes(B, Q, cap), "over": None}
+        self.x_ratio = st.m["sent"] / float(B * self.weight.shape[1] * 4)
+
+    def _masked_over(self, st: _Step) -> bool:
+        """The count check of a masked step, at its consumer: statistics and the capacity of the next
+        steps; True when some rank kept more values than this step's capacity carried.  The step then
+        gathers ya dense, here and once, and goes on as a plain pooled step (every rank saw the same
+        counts, so all take the same branch); ``x_ratio`` then counts both transfers."""
+        m = st.m
+        if m["over"] is None:
+            W = self.world
+            counts = self._zs_counts(m, m["w_meta"], lambda: _counts_of(m["meta_all"], W, m["R"]))
+            mx = max(counts)
+            self.zs_stats["steps"] += 1
+            self.zs_stats["last_nnz"] = counts
+            self._cap["pooled-masked"] = max(1, self._next_cap(m["n"], mx))
+            m["over"] = mx > m["cap"]
+            if m["over"]:
+                self.zs_stats["overflows"] += 1
+                m["w_vals"].wait()
+                self._gather_ya(st, async_op=False)
+                st.w_ya = None
+                self.x_ratio = (m["sent"] + 2 * m["n"]) / float(st.ya.shape[0] * self.weight.shape[1] * 4)
+        return m["over"]
 
     def _pooled_step(self, path: str, source: str, ya, rec, P: int) -> _Step:
         """The record of a step from the pooled input, the all-gather of the head records started
@@ -643,19 +734,31 @@ class ActivationExchange:
         from . import distributed as tdist
 
         st.w_rec.wait()
-        st.w_ya.wait()
+        masked = st.m is not None and not self._masked_over(st)
+        if masked:  # the same steps from (meta, values): bitwise the dense ops' results
+            m, W = st.m, self.world
+            m["w_meta"].wait()
+            m["w_vals"].wait()
+            src = (m["meta_all"].view(W, m["R"]), m["vals_all"].view(W, m["cap"]))
+        else:
+            if st.w_ya is not None:
+                st.w_ya.wait()
+            src = (st.ya_all,)
+        ops = _ext.ops()
         if isinstance(lr, dict):
-            _ext.ops().head_update_pooled_step(dy_all, st.ya_all, st.rec_all, self.weight.data, lr["buf"], st.P, scale,
-                                               lr["lr"], lr["weight_decay"], lr["momentum"], lr["dampening"],
-                                               lr["nesterov"], lr["first_step"])
+            step = ops.head_update_pooled_masked_step if masked else ops.head_update_pooled_step
+            step(dy_all, *src, st.rec_all, self.weight.data, lr["buf"], st.P, scale, lr["lr"], lr["weight_decay"],
+                 lr["momentum"], lr["dampening"], lr["nesterov"], lr["first_step"])
             return
         mode = 0 if lr else (2 if acc else 1)
-        args = (dy_all, st.ya_all, st.rec_all, self.weight.data, None if lr else out, st.P)
-        if st.source == "pooled":
-            _ext.ops().head_update_pooled(*args, scale, float(lr or 0.0), mode)
+        args = (dy_all, *src, st.rec_all, self.weight.data, None if lr else out, st.P)
+        if masked:
+            ops.head_update_pooled_masked(*args, scale, float(lr or 0.0), mode)
+        elif st.source == "pooled":
+            ops.head_update_pooled(*args, scale, float(lr or 0.0), mode)
         else:
             c0, c1 = st.shards[tdist.get_rank(self.group)]
-            _ext.ops().head_update_pooled_shard(*args, c0, c1, scale, float(lr or 0.0), mode)
+            ops.head_update_pooled_shard(*args, c0, c1, scale, float(lr or 0.0), mode)
 
     def begin_groups(self, rows: int, in_f: int, dev, planes: int = 0):
         """Start a grouped zero-suppressed activation exchange: returns the column groups; the caller
