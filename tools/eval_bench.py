@@ -10,6 +10,10 @@ Per shape (``--image-size``, ``--batch-size``), with HIP events and the warm-up 
 * ``conv2``: the isolated inference conv2 launch (``ops.fused_conv2_forward_inference``) beside the
   training launch (``ops.fused_conv2_forward_bn``) on the same p1, packed weights and gamma2.
 
+With ``--precision fp8`` the FP8 (E4M3) conv2 of ``ConvNet(inference_precision="fp8")`` is measured beside
+the TF32-class one: ``fused_fp8`` (the whole eval forward, its windows alternating with ``fused``'s) and
+``conv2.fp8_ms`` (``ops.fused_conv2_forward_inference_fp8`` on the same p1, alternating with the other two).
+
 Every figure is a list over ``--repeats`` timed windows (each ``--iters`` calls), the two arms of a
 comparison alternating inside a repeat.  Needs a GPU: there is no CPU fallback for a timing.
 
@@ -62,6 +66,8 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--input", default="levels", choices=["levels", "fp32"])
+    ap.add_argument("--precision", default="tf32", choices=["tf32", "fp8"],
+                    help="fp8: also measure the FP8 conv2 (forward and isolated launch) beside the TF32-class one")
     ap.add_argument("--skip-layers", action="store_true", help="leave out the mode='layers' arm (sizes it cannot hold)")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -85,15 +91,25 @@ def main(argv=None):
 
     rec = {"metric": "eval_bench", "image_size": H, "batch_size": B, "input": a.input, "iters": a.iters,
            "warmup": a.warmup, "repeats": a.repeats, "device": torch.cuda.get_device_name(dev)}
-    fused_ms, layers_ms = [], []
+    fp8 = a.precision == "fp8"
+    fused_ms, layers_ms, fp8_ms = [], [], []
     for _ in range(a.repeats):  # the arms alternate
         model.mode = "auto"
         fused_ms.append(_time(forward, a.iters, a.warmup))
+        if fp8:
+            model.inference_precision = "fp8"
+            fp8_ms.append(_time(forward, a.iters, a.warmup))
+            model.inference_precision = "tf32"
         if not a.skip_layers:
             model.mode = "layers"
             layers_ms.append(_time(forward, max(2, a.iters // 4), 1))
     model.mode = "auto"
     rec["fused"] = {"ms_per_batch": fused_ms, "peak_mem_bytes": _peak(forward, dev)}
+    if fp8:
+        model.inference_precision = "fp8"
+        rec["fused_fp8"] = {"ms_per_batch": fp8_ms, "peak_mem_bytes": _peak(forward, dev)}
+        model.inference_precision = "tf32"
+        rec["fp8_vs_tf32_forward"] = min(fp8_ms) / min(fused_ms)
     if not a.skip_layers:
         model.mode = "layers"
         rec["layers"] = {"ms_per_batch": layers_ms, "peak_mem_bytes": _peak(forward, dev)}
@@ -121,13 +137,24 @@ def main(argv=None):
         return ops.fused_conv2_forward_bn(p1, wp, conv2.bias, bn2.weight, bn2.bias, rm, rv, nbt, float(bn2.momentum),
                                           float(bn2.eps), mag)
 
-    inf_ms, train_ms = [], []
+    if fp8:  # (a timing: mag keeps the TF32-class pack's store factor for the other two launches; p1's FP8 scale is in it)
+        wp8, wexp = ops.conv2_pack_fp8(conv2.weight.detach(), None)
+
+    def conv2_fp8():
+        return ops.fused_conv2_forward_inference_fp8(p1, wp8, wexp, bn2.weight, mag)
+
+    inf_ms, train_ms, c8_ms = [], [], []
     for _ in range(a.repeats):
         inf_ms.append(_time(conv2_inf, a.iters, a.warmup))
         train_ms.append(_time(conv2_train, a.iters, a.warmup))
+        if fp8:
+            c8_ms.append(_time(conv2_fp8, a.iters, a.warmup))
     same = torch.equal(conv2_inf().view(torch.int16), conv2_train()[1].view(torch.int16))
     rec["conv2"] = {"inference_ms": inf_ms, "training_ms": train_ms, "ya_bit_identical": bool(same),
                     "inference_vs_training": min(inf_ms) / min(train_ms)}
+    if fp8:
+        rec["conv2"]["fp8_ms"] = c8_ms
+        rec["conv2"]["fp8_vs_inference"] = min(c8_ms) / min(inf_ms)
     print(json.dumps(rec), flush=True)
     return rec
 

@@ -61,6 +61,7 @@ HIP_FILE_FLAGS = {
     "x_autocorr.hip": ["-fno-slp-vectorize"],
     "conv2_bwd.hip": ["-fno-slp-vectorize"],
     "conv2_fwd2.hip": ["-fno-slp-vectorize"],
+    "conv2_fwd_fp8.hip": ["-fno-slp-vectorize"],  # (the conv2 kernels' flag: conversion VALU beside the MFMAs)
     # MFMA beside per-element f32 VALU (the 81-tap filter), as the conv2 kernels; results into VGPRs
     "l1_dgrad.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"],
     # the wide head's epilogues read every MFMA tile back (as above); no packed fp32 VALU: its sums and

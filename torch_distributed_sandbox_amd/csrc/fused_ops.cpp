@@ -150,6 +150,8 @@ int64_t pb_plane(int64_t P) { return tds_pb_plane((int)(P / 2)); }
 constexpr int64_t kG2mSlack = 32;   // fp16 elements (64 B) past g2m's end its allocations carry (conv2_bwd.hip GB runs)
 constexpr int64_t kMagParts = 64;   // ypart offset in the mag workspace
 constexpr int64_t kMagScales = 40;  // conv2 epilogue scales (csrc/kernels/conv2_common.h)
+constexpr int64_t kMagP1Fp8 = 45;   // p1's FP8 operand scale, kFp8FragBytes: the E4M3 fragments (csrc/kernels/conv2_fp8.h)
+constexpr int64_t kFp8FragBytes = 16384;
 int64_t mag_ypart_count() { return (int64_t)tds_conv2_fwd2_num_wg(); }
 int64_t mag_gpart_count(int64_t B, int64_t P) {
   return (int64_t)32 * tds_head_bwd_pb_npass((int)B) * tds_head_bwd_pb_nblk((int)(P / 2));
@@ -480,7 +482,8 @@ std::tuple<Tensor, Tensor> inference_constants(const Tensor& x, const Tensor& w1
                           w1.data_ptr<float>(), b1.data_ptr<float>(), g1.data_ptr<float>(), be1.data_ptr<float>(),
                           rm1.data_ptr<float>(), rv1.data_ptr<float>(), (float)eps1, g2.data_ptr<float>(),
                           be2.data_ptr<float>(), rm2.data_ptr<float>(), rv2.data_ptr<float>(), (float)eps2,
-                          aff1.data_ptr<float>(), aff2.data_ptr<float>(), m, st);
+                          aff1.data_ptr<float>(), aff2.data_ptr<float>(), m, st,
+                          /*p1_fp8=*/mag.numel() > kMagP1Fp8);  // (a mag that holds the word gets it)
   check_launches("inference_constants");
   return {aff1, aff2};
 }
@@ -526,6 +529,55 @@ Tensor fused_conv2_forward_inference(const Tensor& p1, const Tensor& wp, const c
   tds_conv2_fwd2_inference(p1.data_ptr(), wp.data_ptr<int16_t>(), g, ya_out(ya), m ? m + kMagScales : nullptr, order,
                            nwg, sw, sk, (int)B, (int)P, stream_of(p1));
   check_launches("fused_conv2_forward_inference");
+  return ya;
+}
+
+// conv2's weights as E4M3 fragments for the FP8 inference conv2 (kernels/conv2_pack.hip
+// conv2_pack_fp8_kernel): returns (wp8 [16384] uint8 in that kernel's B-operand order, wexp [32] int32:
+// the per-channel scale exponents, w_c * 2^wexp[c] is what was rounded).  With mag -- which already holds
+// p1's FP8 scale at [kMagP1Fp8], inference_constants' -- ya's decode words mag[kMagScales] = 1 and
+// mag[kMagScales + 2] = 2^k are written for the conv2 launch and the head.
+std::tuple<Tensor, Tensor> conv2_pack_fp8(const Tensor& w2, const c10::optional<Tensor>& mag) {
+  need(w2, at::kFloat, {32, 16, 5, 5}, "conv2.weight");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w2.data_ptr()) % 16 == 0, "conv2_pack_fp8: conv2.weight must be 16-B aligned");
+  uint32_t* m = opt_mag(mag, kMagP1Fp8 + 1);
+  c10::DeviceGuard guard(w2.device());
+  auto wp8 = at::empty({kFp8FragBytes}, w2.options().dtype(at::kByte));
+  auto wexp = at::empty({32}, w2.options().dtype(at::kInt));
+  tds_conv2_pack_fp8(w2.data_ptr<float>(), wp8.data_ptr(), wexp.data_ptr<int>(), m, stream_of(w2));
+  check_launches("conv2_pack_fp8");
+  return {wp8, wexp};
+}
+
+// The inference conv2 in FP8 (kernels/conv2_fwd_fp8.hip, v_mfma_scale_f32_16x16x128_f8f6f4): ya [B,32,PB]
+// fp16 in fused_conv2_forward_inference's format, from p1 as layer 1 writes it, conv2_pack_fp8's
+// fragments and exponents, and mag: 2^k at [kMagScales + 2] (the pack's) and p1's FP8 scale at
+// [kMagP1Fp8] (inference_constants').  Everything is checked before ya is allocated.
+Tensor fused_conv2_forward_inference_fp8(const Tensor& p1, const Tensor& wp8, const Tensor& wexp,
+                                         const c10::optional<Tensor>& gamma2, const Tensor& mag) {
+  TORCH_CHECK(p1.dim() == 4 && p1.size(1) == p1.size(2) && p1.size(3) == 16,
+              "fused_conv2_forward_inference_fp8: p1 [B,P,P,16]");
+  const int64_t B = p1.size(0), P = p1.size(1);
+  need(p1, at::kHalf, {B, P, P, 16}, "p1");
+  need(wp8, at::kByte, {kFp8FragBytes}, "conv2 fp8 pack");
+  need(wexp, at::kInt, {32}, "conv2 fp8 scale exponents");
+  const float* g = optf(gamma2, 32, "bn2.weight");
+  TORCH_CHECK(B >= 1 && B <= 255 && P >= 2 && P % 2 == 0,
+              "fused_conv2_forward_inference_fp8: 1 <= batch <= 255 and an even P >= 2");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(p1.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(wp8.data_ptr()) % 16 == 0,
+              "fused_conv2_forward_inference_fp8: p1 and the pack must be 16-B aligned");
+  const uint32_t* m = opt_mag(mag, kMagP1Fp8 + 1);
+  TORCH_CHECK(m != nullptr, "fused_conv2_forward_inference_fp8: mag is required");
+  c10::DeviceGuard guard(p1.device());
+  const int nwg = tds_conv2_fwd2_num_wg();  // (conv2_fwd2's tile size and workgroup count: one order table)
+  int tr = 0, tc = 0;
+  tds_conv2_fwd_fp8_tiles((int)P, &tr, &tc);
+  int sw = 0, sk = 0;
+  const int* order = tile_order(p1, (int)B, tr, tc, nwg, &sw, &sk);
+  auto ya = at::empty({B, 32, pb_plane(P)}, p1.options().dtype(at::kHalf));
+  tds_conv2_fwd_fp8(p1.data_ptr(), wp8.data_ptr(), wexp.data_ptr<int>(), g, ya_out(ya), m, order, nwg, sw, sk, (int)B,
+                    (int)P, stream_of(p1));
+  check_launches("fused_conv2_forward_inference_fp8");
   return ya;
 }
 
@@ -1691,6 +1743,9 @@ TORCH_LIBRARY_FRAGMENT(tdsa, m) {
         &fused_l1_forward_inference);
   m.def("fused_conv2_forward_inference(Tensor p1, Tensor wp, Tensor? gamma2, Tensor? mag=None) -> Tensor",
         &fused_conv2_forward_inference);
+  m.def("conv2_pack_fp8(Tensor w2, Tensor(a!)? mag=None) -> (Tensor, Tensor)", &conv2_pack_fp8);
+  m.def("fused_conv2_forward_inference_fp8(Tensor p1, Tensor wp8, Tensor wexp, Tensor? gamma2, Tensor mag) -> Tensor",
+        &fused_conv2_forward_inference_fp8);
   m.def("eval_metrics(Tensor logits, Tensor labels, Tensor(a!) acc) -> ()", &eval_metrics);
   m.def("fused_head_forward_aff(Tensor ya, Tensor aff2, Tensor b2, Tensor? mag, Tensor wfc, Tensor? bfc, int P, "
         "Tensor(a!)? x_out=None) -> Tensor",

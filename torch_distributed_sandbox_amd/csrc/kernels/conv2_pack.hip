@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "conv2_common.h"
+#include "conv2_fp8.h"
 #include "conv2_pack.h"
 #include "launchers.h"
 
@@ -76,9 +77,81 @@ __global__ __launch_bounds__(64 * WGR_WAVES) void conv2_wgrad_reduce_kernel(cons
   else if (db && ci == 0) db[co] = v;
 }
 
+// ---------------------------------------------------------------------------- FP8 weight packing
+// The inference plan's FP8 conv2 (conv2_fwd_fp8.hip): w2 as E4M3 fragments in that kernel's B-operand
+// order, wp8[nt<2][s<4][h<2][lane 64][ci16] bytes (conv2_fp8.h: lane = 16 g + co16, tap pair q = 4s + g,
+// tap (ky, kx + h); kx + h = 5 and q = 15 -> zero), each output channel at its own power of two:
+// wexp[co] = ew with max |w_co| * 2^ew in (224, 448] (E4M3's top binade; 0 for an all-zero channel).
+// w * 2^ew is exact in fp32 and rounded once, to nearest even, by v_cvt_pk_fp8_f32.  mag (optional; it
+// holds p1's FP8 scale 2^ep at mag[kMagP1Fp8], so inference_constants goes first): mag[kMagScales] = 1
+// and mag[kMagScales + 2] = 2^k, ya's store factor -- the largest |y2 - b2| / (1 / p1 scale) the
+// quantised operands can make, 1.14 * 448 * 2^-ep * max_c sum |w_c| (1.14 > (1 + 2^-4)^2: both operands
+// rounded up), times 2^k stays below 2^15 -- so the head's decode of ya (launchers.h TdsYaDec) needs no
+// change and a channel 2^-17 of the largest still stores normal fp16 values.  One workgroup: 12 800 weights.
+__global__ __launch_bounds__(256) void conv2_pack_fp8_kernel(const float* __restrict__ w2, uint32_t* __restrict__ wp8,
+                                                             int* __restrict__ wexp, uint32_t* __restrict__ mag) {
+  __shared__ float sc[32], red[4];
+  const int tid = threadIdx.x;
+  {
+    // channel c = tid / 8: 100 float4, 8 lanes each, summed in a fixed order
+    const float4* w4 = reinterpret_cast<const float4*>(w2);
+    const int c = tid >> 3, j = tid & 7;
+    float m = 0.f, l1 = 0.f;
+    for (int k = j; k < 100; k += 8) {
+      const float4 q = w4[c * 100 + k];
+      m = fmaxf(m, fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fmaxf(fabsf(q.z), fabsf(q.w))));  // NaN: ignored
+      l1 += (fabsf(q.x) + fabsf(q.y)) + (fabsf(q.z) + fabsf(q.w));
+    }
+#pragma unroll
+    for (int off = 1; off < 8; off <<= 1) {
+      m = fmaxf(m, __shfl_xor(m, off, 64));
+      l1 += __shfl_xor(l1, off, 64);
+    }
+    const int ew = f8_scale_exp((double)m);
+    if (j == 0) {
+      sc[c] = ldexpf(1.f, ew);
+      wexp[c] = ew;
+    }
+    l1 = wave_max(l1);
+    if ((tid & 63) == 0) red[tid >> 6] = l1;
+  }
+  __syncthreads();
+  if (tid == 0 && mag != nullptr) {
+    // |acc| 2^-ew 2^-ep <= (1 + 2^-4)^2 * (448 * 2^-ep) * max_c sum |w_c| =: T (both roundings up, p1 at its
+    // bound), and T * 2^k < 2^15
+    const float L = 1.14f * fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    const float T = L * F8_E4M3_MAX / __uint_as_float(mag[kMagP1Fp8]);
+    int k = 0;
+    if (T > 0.f && __builtin_isfinite(T)) {
+      int x;
+      (void)frexpf(T, &x);  // T < 2^x
+      k = min(100, max(-100, 15 - x));
+    }
+    mag[kMagScales] = __float_as_uint(1.f);
+    mag[kMagScales + 2] = __float_as_uint(ldexpf(1.f, k));
+  }
+  for (int e = tid; e < F8_WFRAG_BYTES / 4; e += 256) {  // word e: channels 4 (e & 3) .. +3 of one lane's tap
+    const int c4 = e & 3, lane = (e >> 2) & 63, h = (e >> 8) & 1, s = (e >> 9) & 3, nt = e >> 11;
+    const int q = 4 * s + (lane >> 4), co = 16 * nt + (lane & 15);
+    const int ky = f8_pair_ky(q), kx = f8_pair_kx(q) + h;
+    uint32_t word = 0u;
+    if (q < 15 && kx < 5) {
+      const float* src = w2 + (co * 16 + 4 * c4) * 25 + ky * 5 + kx;
+      const float f = sc[co];
+      word = f8_pack4(src[0] * f, src[25] * f, src[50] * f, src[75] * f);
+    }
+    wp8[e] = word;
+  }
+}
+
 }  // namespace tds
 
 using namespace tds;
+
+void tds_conv2_pack_fp8(const float* w2, void* wp8, int* wexp, uint32_t* mag, hipStream_t st) {
+  hipLaunchKernelGGL(conv2_pack_fp8_kernel, dim3(1), dim3(256), 0, st, w2, static_cast<uint32_t*>(wp8), wexp, mag);
+  TDS_LAUNCH_CHECK();
+}
 
 void tds_conv2_pack_weights(const float* w2, short* wp, short* wd, uint32_t* mag, const float* p1_scale,
                             hipStream_t st, bool write_p1) {

@@ -9,7 +9,7 @@
 #include <algorithm>
 
 #include "ce_small.h"
-#include "conv2_common.h"
+#include "conv2_fp8.h"
 #include "launchers.h"
 
 namespace tds {
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void inference_constants_kernel(
     const float* __restrict__ b1, const float* __restrict__ g1, const float* __restrict__ be1,
     const float* __restrict__ rm1, const float* __restrict__ rv1, float eps1, const float* __restrict__ g2,
     const float* __restrict__ be2, const float* __restrict__ rm2, const float* __restrict__ rv2, float eps2,
-    float* __restrict__ aff1, float* __restrict__ aff2, uint32_t* __restrict__ p1inv) {
+    float* __restrict__ aff1, float* __restrict__ aff2, uint32_t* __restrict__ p1inv, uint32_t* __restrict__ p1q) {
   __shared__ uint32_t sh[4];
   const int tid = threadIdx.x;
   float xmax = xmax_fixed;
@@ -81,6 +81,12 @@ __global__ __launch_bounds__(256) void inference_constants_kernel(
     if (tid == 0) {
       aff1[32] = p1_scale;
       *p1inv = __float_as_uint(1.f / p1_scale);
+      // the FP8 conv2's operand scale (conv2_fwd_fp8.hip): the power of two that takes the stored p1's
+      // bound to at most 448 (a bound that is not finite leaves fp16's own, 65504)
+      if (p1q != nullptr) {
+        const double bh = __builtin_isfinite(bound) ? fmin(bound * (double)p1_scale, 65504.0) : 65504.0;
+        *p1q = __float_as_uint(ldexpf(1.f, f8_scale_exp(bh)));
+      }
     }
     if (tid < 16) {
       aff1[c] = a * p1_scale;
@@ -176,9 +182,10 @@ void tds_x_absmax(const float* x, int64_t n4, uint32_t* part, int nwg, hipStream
 void tds_inference_constants(const uint32_t* xpart, int nxp, const float* w1, const float* b1, const float* g1,
                              const float* be1, const float* rm1, const float* rv1, float eps1, const float* g2,
                              const float* be2, const float* rm2, const float* rv2, float eps2, float* aff1, float* aff2,
-                             uint32_t* mag, hipStream_t st) {
+                             uint32_t* mag, hipStream_t st, bool p1_fp8) {
   hipLaunchKernelGGL(inference_constants_kernel, dim3(1), dim3(256), 0, st, xpart, nxp, 255.f * INF_LEVEL_SCALE, w1, b1,
-                     g1, be1, rm1, rv1, eps1, g2, be2, rm2, rv2, eps2, aff1, aff2, mag + kMagScales + 1);
+                     g1, be1, rm1, rv1, eps1, g2, be2, rm2, rv2, eps2, aff1, aff2, mag + kMagScales + 1,
+                     p1_fp8 ? mag + kMagP1Fp8 : nullptr);
   TDS_LAUNCH_CHECK();
 }
 

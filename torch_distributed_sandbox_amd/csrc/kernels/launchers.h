@@ -111,6 +111,14 @@ void tds_conv2_fwd2(const void* p1, const short* wp, const float* bias, const fl
 void tds_conv2_fwd2_inference(const void* p1, const short* wp, const float* gamma, unsigned short* ya,
                               const uint32_t* scales, const int* order, int nwg, int sw, int sk, int B, int P,
                               hipStream_t st);
+// ---- conv2_fwd_fp8.hip / conv2_pack.hip: the inference plan's FP8 (E4M3) conv2 on the block-scaled MFMA
+// wp8: 16 384 fragment bytes, wexp [32]: the per-channel scale exponents; mag (optional): ya's decode words
+void tds_conv2_pack_fp8(const float* w2, void* wp8, int* wexp, uint32_t* mag, hipStream_t st);
+void tds_conv2_fwd_fp8_tiles(int P, int* tiles_r, int* tiles_c);
+// ya as tds_conv2_fwd2_inference writes it; mag: kMagScales + 6 words (2^k at [42], p1's FP8 scale at [45]);
+// order / nwg / sw / sk as tds_conv2_fwd2
+void tds_conv2_fwd_fp8(const void* p1, const void* wp8, const int* wexp, const float* gamma, unsigned short* ya,
+                       const uint32_t* mag, const int* order, int nwg, int sw, int sk, int B, int P, hipStream_t st);
 int tds_conv2_bwd3_num_wg();  // slab rows the backward writes (workgroups it launches)
 void tds_conv2_bwd3_tiles(int P, int* tiles_r, int* tiles_c);
 // rolling-window backward (conv2_bwd.hip): walk = tds_conv2_bwd_walk table for nwg workgroups
@@ -203,11 +211,12 @@ int tds_x_absmax_num_wg(int64_t n4);  // partial words tds_x_absmax writes for n
 void tds_x_absmax(const float* x, int64_t n4, uint32_t* part, int nwg, hipStream_t st);  // max |x| bits per workgroup
 // aff1 [33] (a16 | b16 | p1 scale) and aff2 [64] (a32 | b32) from the running statistics, and
 // mag[kMagScales + 1] = 1 / p1 scale.  xpart (nxp words of tds_x_absmax) bounds an fp32 input;
-// nullptr: uint8 levels, |x| <= 255 / 255.  No BN buffer is written.
+// nullptr: uint8 levels, |x| <= 255 / 255.  No BN buffer is written.  p1_fp8: also mag[kMagScales + 5] =
+// 2^ep, the FP8 conv2's p1 operand scale (conv2_fp8.h kMagP1Fp8).
 void tds_inference_constants(const uint32_t* xpart, int nxp, const float* w1, const float* b1, const float* g1,
                              const float* be1, const float* rm1, const float* rv1, float eps1, const float* g2,
                              const float* be2, const float* rm2, const float* rv2, float eps2, float* aff1, float* aff2,
-                             uint32_t* mag, hipStream_t st);
+                             uint32_t* mag, hipStream_t st, bool p1_fp8 = false);
 // acc [3] += (fp64 sum of per-sample cross-entropy | correct argmax count | samples counted)
 void tds_eval_metrics(const float* logits, const int64_t* labels, int M, int N, int64_t ignore_index,
                       unsigned long long* acc, hipStream_t st);

@@ -26,12 +26,15 @@ Differences from the reference, by design:
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 
 from ..ops import modules as M
 
 IMAGE_SHAPE = (3000, 3000)
+INFERENCE_PRECISIONS = ("tf32", "fp8")
 LEVEL_SCALE = 1.0 / 255.0  # fp32(1/255): the scale ToTensor and the upsample kernel apply to uint8 levels
 
 
@@ -49,7 +52,8 @@ def fc_in_features(image_shape, channels: int = 32) -> int:
 
 
 class ConvNet(nn.Module):
-    def __init__(self, num_classes: int = 10, image_shape=IMAGE_SHAPE, device=None, mode: str = "auto"):
+    def __init__(self, num_classes: int = 10, image_shape=IMAGE_SHAPE, device=None, mode: str = "auto",
+                 inference_precision: str = "tf32"):
         super().__init__()
         self.image_shape = tuple(image_shape)
         self.layer1 = nn.Sequential(
@@ -68,6 +72,17 @@ class ConvNet(nn.Module):
         if mode not in ("auto", "fused", "layers"):
             raise ValueError(f"mode must be auto|fused|layers, got {mode!r}")
         self.mode = mode
+        # conv2's operand type in the fused inference plan (convnet_fused.forward_inference): "tf32", the
+        # training numerics, or "fp8", E4M3 operands on the block-scaled MFMA (opt-in: 4 significant
+        # bits).  mode="layers" and the training plan ignore it.  A non-empty TDS_INFERENCE_PRECISION
+        # overrides the argument: the operator's switch (like DDP's TDS_EXCHANGE_SOURCE).
+        env_precision = os.environ.get("TDS_INFERENCE_PRECISION", "").strip()
+        if env_precision:
+            inference_precision = env_precision
+        if inference_precision not in INFERENCE_PRECISIONS:
+            raise ValueError(
+                f"inference_precision must be {'|'.join(INFERENCE_PRECISIONS)}, got {inference_precision!r}")
+        self.inference_precision = inference_precision
 
     # ------------------------------------------------------------------ plans
     def _forward_layers(self, x):

@@ -186,7 +186,8 @@ def _sinks(ctx, params, first):
 _ZERO = {}
 # counters the tests read: forward passes that applied the exchange's weight update in the head kernel,
 # and layer-1 forwards that took x moments precomputed by the input pipeline
-STATS = {"precomputed_input_moments": 0, "head_fused_ce": 0, "head_range_launches": 0, "head_wide": 0}
+STATS = {"precomputed_input_moments": 0, "head_fused_ce": 0, "head_range_launches": 0, "head_wide": 0,
+         "inference_fp8": 0}
 
 
 def _zero_scalar(device, dtype):
@@ -578,7 +579,10 @@ def forward(model, x):
 # No autograd Function, link, gradient sink or exchange is involved, and every workspace (mag
 # included) is this call's own: an eval forward between a training forward and its backward leaves
 # that step as it was.
-_INFERENCE_MAG = 48  # the bounds conv2_pack zeroes (33 words) and the scales at kMagScales = 40 .. 43
+# ConvNet(inference_precision="fp8") swaps the two conv2 launches for their E4M3 forms (conv2_pack_fp8,
+# fused_conv2_forward_inference_fp8: v_mfma_scale_f32_16x16x128_f8f6f4); ya's format and the head are
+# the same, the decode words in mag describe the FP8 kernel's scales.
+_INFERENCE_MAG = 48  # the bounds conv2_pack zeroes (33 words), the scales at kMagScales = 40 .. 43, p1's FP8 scale at 45
 
 
 def forward_inference(model, x):
@@ -589,12 +593,20 @@ def forward_inference(model, x):
     x = x.contiguous()
     param_fence.wait(conv2.weight)  # a deferred update of the weights (overlap_optimizer) lands first
     mag = torch.empty(_INFERENCE_MAG, device=x.device, dtype=torch.int32)
-    wp, _ = ops.conv2_pack(conv2.weight.detach().contiguous(), mag, None, False)
+    fp8 = getattr(model, "inference_precision", "tf32") == "fp8"
+    if not fp8:
+        wp, _ = ops.conv2_pack(conv2.weight.detach().contiguous(), mag, None, False)
     aff1, aff2 = ops.inference_constants(x, conv1.weight, conv1.bias, bn1.weight, bn1.bias, bn1.running_mean,
                                          bn1.running_var, float(bn1.eps), bn2.weight, bn2.bias, bn2.running_mean,
                                          bn2.running_var, float(bn2.eps), mag)
     p1 = ops.fused_l1_forward_inference(x, conv1.weight, conv1.bias, aff1)
-    ya = ops.fused_conv2_forward_inference(p1, wp, bn2.weight, mag)
+    if fp8:
+        # (after the constants: ya's store factor takes p1's FP8 scale from mag)
+        wp, wexp = ops.conv2_pack_fp8(conv2.weight.detach().contiguous(), mag)
+        ya = ops.fused_conv2_forward_inference_fp8(p1, wp, wexp, bn2.weight, mag)
+        STATS["inference_fp8"] += 1
+    else:
+        ya = ops.fused_conv2_forward_inference(p1, wp, bn2.weight, mag)
     # the fc update may still be running on DDP's side stream, or deferred to the next head forward
     # (forward() above): it lands before the weight is read
     upd = param_fence.take(fc.weight, "groups")

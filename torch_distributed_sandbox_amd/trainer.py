@@ -74,6 +74,9 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                         "(0 = no evaluation)")
     p.add_argument("--eval-batch-size", default=None, type=int,
                    help="per-GPU batch size of the evaluation (default: --batch-size)")
+    p.add_argument("--eval-precision", default="tf32", choices=["tf32", "fp8"],
+                   help="conv2 operands of the fused inference plan (evaluation): tf32, the training numerics, "
+                        "or fp8 (E4M3 on the block-scaled MFMA)")
     return p
 
 
@@ -190,7 +193,8 @@ def train(gpu: int, args, distributed: bool = False) -> dict:
     device = _device(args, gpu)
     torch.manual_seed(0)
     H = W = args.image_size
-    model = ConvNet(num_classes=args.num_classes, image_shape=(H, W), device=device, mode=args.mode)
+    model = ConvNet(num_classes=args.num_classes, image_shape=(H, W), device=device, mode=args.mode,
+                    inference_precision=getattr(args, "eval_precision", "tf32"))
     batch_size = args.batch_size
     criterion = CrossEntropyLoss()
     opt_args = {"momentum": float(getattr(args, "momentum", 0.0)), "weight_decay": float(getattr(args, "weight_decay", 0.0)),
