@@ -160,6 +160,10 @@ void tds_x_border_u8(const uint8_t* x, double* strips, int B, int H, int W, hipS
 int tds_ups_moments_rows(int B, int h, int w, int H, int W);
 void tds_ups_moments_u8(const uint8_t* src, uint8_t* x, double* partial, int nrows, int B, int h, int w, int H, int W,
                         hipStream_t st);  // the same moments of uint8 levels (exact)
+// the same through a per-image affine map, mats [B][6] (ups_affine.hip): partial rows, 0 = unsupported shape
+int tds_ups_affine_rows(int B, int h, int w, int H, int W);
+void tds_ups_affine_moments_u8(const uint8_t* src, const float* mats, uint8_t* x, double* partial, int nrows, int B,
+                               int h, int w, int H, int W, hipStream_t st);
 int tds_conv2_bwd_clock_read(uint32_t* host, int n);  // DIAG 13 per-wave barrier clocks (diag builds)
 void tds_x_border(const float* x, double* strips, int B, int H, int W, hipStream_t st);  // border strips [B][8][82]
 void tds_reduce_partials(const double* in, double* out, int n, int nchunk, int inner, int64_t ostride, int64_t kstride,

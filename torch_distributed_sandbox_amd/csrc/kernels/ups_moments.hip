@@ -19,40 +19,14 @@
 // plain-sum dot4 per quad and row, ring slots static (the row loop unrolled by 5).  The source
 // image (784 floats) sits in LDS; a thread keeps its columns' horizontal taps and the two
 // horizontally interpolated source rows of the current vertical tap pair, recomputed when the
-// pair changes (about every H/h rows).
+// pair changes (about every H/h rows).  The work split and the moments half live in um_ring.h,
+// shared with the affine-sampling variant (ups_affine.hip).
 #include "common.h"
 #include "launchers.h"
 #include "ups_common.h"
-#include "xmom_u8.h"
+#include "um_ring.h"
 
 namespace tds {
-
-// (isolated op, r5_s35: 32 rows 48.1 - 48.6 us, 40: 47.0 - 48.6, 48: 45.8 - 46.2, 64: 45.3 - 46.7)
-constexpr int UM_RB = 48;         // output rows per wave
-constexpr int UM_QPW = 62;        // quads per wave at most (lanes 1..62 own them)
-// a lane's sums: UM_RB rows x 4 products <= 255^2 each; the wave's: 62 lanes
-static_assert((unsigned long long)UM_RB * 4ull * 62ull * 65025ull < (1ull << 32), "u32 wave sums would wrap");
-
-struct UmGeo {
-  int nqg, qpw, nband;
-};
-static UmGeo um_geo(int H, int W) {
-  UmGeo g;
-  const int nq = W / 4;
-  g.nqg = (nq + UM_QPW - 1) / UM_QPW;
-  g.qpw = (nq + g.nqg - 1) / g.nqg;
-  g.nband = (H + UM_RB - 1) / UM_RB;
-  return g;
-}
-
-__device__ __forceinline__ uint32_t um_shr1(uint32_t v) {  // lane l <- lane l - 1 (lane 0 <- 0)
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, true);
-}
-__device__ __forceinline__ uint32_t um_shl1(uint32_t v) {  // lane l <- lane l + 1 (lane 63 <- 0)
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xF, 0xF, true);
-}
-
-typedef float um_f2 __attribute__((ext_vector_type(2)));
 
 __global__ __launch_bounds__(64) void ups_moments_u8_kernel(const uint8_t* __restrict__ src,
                                                             uint8_t* __restrict__ x, double* __restrict__ partial,
@@ -101,7 +75,6 @@ __global__ __launch_bounds__(64) void ups_moments_u8_kernel(const uint8_t* __res
   const int r0 = band * UM_RB;
   // the vertical taps of the wave's rows r0 .. r0 + UM_RB + 3, lane i holding row r0 + i's (read
   // back per row with v_readlane: one instruction each instead of the tap arithmetic per row)
-  static_assert(UM_RB + 4 <= 64, "one lane per row of the band");
   int ty0 = 0, ty1 = 0;
   float tay = 0.f;
   ups_taps(min(r0 + lane, H - 1), sy, h, ty0, ty1, tay);
@@ -138,21 +111,7 @@ __global__ __launch_bounds__(64) void ups_moments_u8_kernel(const uint8_t* __res
           cur = vq ? (l0 | (l1 << 8) | (l2 << 16) | (l3 << 24)) : 0u;
           if (own && i < UM_RB) xrow[(int64_t)i * (W >> 2)] = cur;
         }
-        const uint32_t left = um_shr1(cur), right = um_shl1(cur);
-#pragma unroll
-        for (int s9 = 0; s9 < 9; ++s9) ring[j][s9] = xm_win(left, cur, right, s9);
-        if (i >= 4) {  // the band's row i - 4 against rows i - 4 .. i (ring slots j+1 .. j+5 mod 5)
-          const uint32_t u = own ? ring[(j + 1) % 5][4] : 0u;
-          int k = 0;
-#pragma unroll
-          for (int dx = 0; dx <= 4; ++dx, ++k) acc[k] = __builtin_amdgcn_udot4(u, ring[(j + 1) % 5][4 + dx], acc[k], false);
-#pragma unroll
-          for (int dy = 1; dy <= 4; ++dy)
-#pragma unroll
-            for (int dx = -4; dx <= 4; ++dx, ++k)
-              acc[k] = __builtin_amdgcn_udot4(u, ring[(j + 1 + dy) % 5][4 + dx], acc[k], false);
-          acc[41] = __builtin_amdgcn_udot4(u, 0x01010101u, acc[41], false);
-        }
+        um_row(ring, acc, i, j, cur, own);
       }
     }
   }

@@ -127,6 +127,31 @@ std::tuple<Tensor, Tensor> upsample_levels_moments(const Tensor& src, int64_t H,
   return {dst, part};
 }
 
+// The same op sampling the source through a per-image affine map (ups_affine.hip: random-affine
+// augmentation), mats [B,6] fp32 = (m00 m01 m02 m10 m11 m12) taking output pixel centres to source
+// pixel indices.  Shapes the kernel does not take are refused: there is no other affine path.
+std::tuple<Tensor, Tensor> upsample_levels_moments_affine(const Tensor& src, const Tensor& mats, int64_t H, int64_t W) {
+  TORCH_CHECK(src.is_cuda() && src.scalar_type() == at::kByte && src.is_contiguous() && src.dim() == 3,
+              "tdsa.upsample_levels_moments_affine: expected contiguous uint8 [B,h,w] on GPU");
+  check_f32_dev(mats, "mats");
+  TORCH_CHECK(mats.device() == src.device() && mats.dim() == 2 && mats.size(0) == src.size(0) && mats.size(1) == 6,
+              "tdsa.upsample_levels_moments_affine: mats must be [B,6] on the source's device");
+  const int64_t B = src.size(0), h = src.size(1), w = src.size(2);
+  const int rows = (B >= 1 && B <= 65535 && h >= 1 && w >= 1 && h * w <= 4096 && H >= 8 && W >= 8 && H <= INT32_MAX &&
+                    W <= INT32_MAX)
+                       ? tds_ups_affine_rows((int)B, (int)h, (int)w, (int)H, (int)W)
+                       : 0;
+  TORCH_CHECK(rows > 0, "tdsa.upsample_levels_moments_affine: unsupported shape (needs W % 4 == 0, W >= 8, H >= 8, ",
+              "source h * w <= 4096, 1 <= B <= 65535), got source ", h, "x", w, ", output ", H, "x", W, ", B ", B);
+  c10::DeviceGuard g(src.device());
+  auto dst = at::empty({B, 1, H, W}, src.options());
+  auto part = at::empty({(int64_t)rows, 42}, src.options().dtype(at::kDouble));
+  tds_ups_affine_moments_u8(src.data_ptr<uint8_t>(), mats.data_ptr<float>(), dst.data_ptr<uint8_t>(),
+                            part.data_ptr<double>(), rows, (int)B, (int)h, (int)w, (int)H, (int)W, cur_stream(src));
+  check_launches("upsample_levels_moments_affine");
+  return {dst, part};
+}
+
 void sgd_step_(at::TensorList params, at::TensorList grads, at::TensorList moms, double lr, double wd,
                double momentum, double dampening, bool nesterov, bool first_step) {
   TORCH_CHECK(params.size() == grads.size(), "tdsa.sgd_step_: params/grads length mismatch");
@@ -435,6 +460,8 @@ TORCH_LIBRARY(tdsa, m) {
   m.def("maxpool2_bwd(Tensor grad, Tensor idx, int H, int W) -> Tensor", &maxpool2_bwd);
   m.def("upsample_bilinear_u8(Tensor src, int H, int W, bool levels=False) -> Tensor", &upsample_bilinear_u8);
   m.def("upsample_levels_moments(Tensor src, int H, int W) -> (Tensor, Tensor)", &upsample_levels_moments);
+  m.def("upsample_levels_moments_affine(Tensor src, Tensor mats, int H, int W) -> (Tensor, Tensor)",
+        &upsample_levels_moments_affine);
   m.def(
       "sgd_step_(Tensor(a!)[] params, Tensor[] grads, Tensor(b!)[] moms, float lr, float weight_decay, float momentum, "
       "float dampening, bool nesterov, bool first_step) -> ()",

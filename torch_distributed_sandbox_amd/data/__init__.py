@@ -1,4 +1,4 @@
 """Synthetic MNIST-like data with on-device upscaling."""
-from .synthetic import MNIST_TRAIN_SIZE, DeviceUpsampleLoader, SyntheticMNIST, synthetic_batch
+from .synthetic import MNIST_TRAIN_SIZE, DeviceUpsampleLoader, RandomAffine, SyntheticMNIST, synthetic_batch
 
-__all__ = ["SyntheticMNIST", "DeviceUpsampleLoader", "synthetic_batch", "MNIST_TRAIN_SIZE"]
+__all__ = ["SyntheticMNIST", "DeviceUpsampleLoader", "RandomAffine", "synthetic_batch", "MNIST_TRAIN_SIZE"]

@@ -19,7 +19,8 @@ is no torchvision and no network here, so:
 from __future__ import annotations
 
 import math
-from typing import Optional, Sequence
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -88,6 +89,32 @@ class SyntheticMNIST:
         return torch.from_numpy(self.images[idx]), torch.from_numpy(self.labels[idx])
 
 
+@dataclass(frozen=True)
+class RandomAffine:
+    """Random-affine augmentation drawn like torchvision's ``RandomAffine``: per image a rotation
+    theta ~ U(-degrees, degrees) and a scale s ~ U(scale) about the image centre, then a shift
+    tx ~ U(-translate w, translate w), ty ~ U(-translate h, translate h) in source pixels."""
+
+    degrees: float = 0.0
+    translate: float = 0.0
+    scale: Tuple[float, float] = (1.0, 1.0)
+
+    def matrices(self, n: int, h: int, w: int, H: int, W: int, rng: np.random.Generator) -> torch.Tensor:
+        """``[n, 6]`` fp32 matrices for ``ops.functional.upsample_levels_moments(affine=...)``: the
+        inverse of the drawn map composed with the output-to-source scale, built in fp64.  It takes
+        an output pixel centre (X + .5, Y + .5) to source pixel indices (the -0.5 folded in)."""
+        th = np.deg2rad(rng.uniform(-self.degrees, self.degrees, n))
+        sc = rng.uniform(self.scale[0], self.scale[1], n)
+        tx = rng.uniform(-self.translate * w, self.translate * w, n)
+        ty = rng.uniform(-self.translate * h, self.translate * h, n)
+        # source point p of the warped image's point p': p = c + R(-theta) (p' - c - t) / s
+        a00, a01, a10, a11 = np.cos(th) / sc, np.sin(th) / sc, -np.sin(th) / sc, np.cos(th) / sc
+        cx, cy = w / 2.0, h / 2.0
+        m = np.stack([a00 * (w / W), a01 * (h / H), cx - a00 * (cx + tx) - a01 * (cy + ty) - 0.5,
+                      a10 * (w / W), a11 * (h / H), cy - a10 * (cx + tx) - a11 * (cy + ty) - 0.5], axis=1)
+        return torch.from_numpy(m.astype(np.float32))
+
+
 class DeviceUpsampleLoader:
     """``DataLoader(dataset, batch_size, sampler/shuffle)`` equivalent that yields
     ``(images[B,1,H,W] f32 on device, labels[B] i64 on device)``.
@@ -100,12 +127,19 @@ class DeviceUpsampleLoader:
     288 GB) and each epoch's sample order is gathered into it once (one kernel per epoch), so a
     step's batch is a view of that buffer: no per-step host indexing, pinning or H2D copy -- the
     step's only input work is the upsample kernel, queued without waiting on the host.  On the
-    CPU batches are gathered per step as the reference's DataLoader does."""
+    CPU batches are gathered per step as the reference's DataLoader does.
+
+    ``augment`` (a :class:`RandomAffine`, needs ``levels=True``): every image is sampled through an
+    affine map of its own by the same single kernel (csrc/kernels/ups_affine.hip), the partials
+    attached.  An epoch's matrices are drawn once, from (seed, epoch, the sampler's rank), in the
+    order of the epoch's gathered sources; a step takes a slice."""
 
     def __init__(self, dataset: SyntheticMNIST, batch_size: int, image_shape, device, sampler=None,
                  shuffle: bool = False, seed: int = 0, drop_last: bool = False, levels: bool = False,
-                 moments: bool = False):
-        self.levels = levels
+                 moments: bool = False, augment: Optional[RandomAffine] = None):
+        if augment is not None and not levels:
+            raise ValueError("augment needs levels=True (the affine input op writes uint8 levels)")
+        self.levels, self.augment = levels, augment
         # levels on the GPU: the upsample also forms the batch's x autocorrelation partials and
         # attaches them for the fused ConvNet plan's BN1 statistics (ops.functional.upsample_levels_moments)
         self.moments = moments and levels
@@ -134,6 +168,12 @@ class DeviceUpsampleLoader:
         n = len(self.sampler) if self.sampler is not None else len(self.dataset)
         return n // self.batch_size if self.drop_last else math.ceil(n / self.batch_size)
 
+    def _epoch_matrices(self, n: int) -> torch.Tensor:
+        rank = int(getattr(self.sampler, "rank", 0) or 0)
+        rng = np.random.default_rng((0xAFF1, int(self.seed), int(self.epoch), rank))
+        h, w = self.dataset.images.shape[1:]
+        return self.augment.matrices(n, h, w, self.H, self.W, rng)
+
     def _resident(self):
         """The dataset's images and labels in device memory (uploaded once)."""
         r = getattr(self, "_dev", None)
@@ -150,25 +190,31 @@ class DeviceUpsampleLoader:
             order = torch.tensor(idx, dtype=torch.int64).to(self.device, non_blocking=False)
             ep_src = imgs.index_select(0, order)  # this epoch's order, one gather
             ep_lab = labs.index_select(0, order)
+            ep_mat = self._epoch_matrices(len(idx)).to(self.device) if self.augment is not None else None
             for s in range(0, len(idx), self.batch_size):
                 e = min(len(idx), s + self.batch_size)
                 if self.drop_last and e - s < self.batch_size:
                     break
-                if self.moments:
+                if self.moments or ep_mat is not None:
                     from ..models import convnet_fused
 
-                    x, part = TF.upsample_levels_moments(ep_src[s:e], self.H, self.W)
+                    x, part = TF.upsample_levels_moments(ep_src[s:e], self.H, self.W,
+                                                         affine=None if ep_mat is None else ep_mat[s:e])
                     if part is not None:
                         convnet_fused.attach_input_stats(x, (part, None))
                     yield x, ep_lab[s:e]
                     continue
                 yield TF.upsample_bilinear_u8(ep_src[s:e], self.H, self.W, levels=self.levels), ep_lab[s:e]
             return
+        ep_mat = self._epoch_matrices(len(idx)) if self.augment is not None else None
         for s in range(0, len(idx), self.batch_size):
             b = idx[s: s + self.batch_size]
             if self.drop_last and len(b) < self.batch_size:
                 break
             src, lab = self.dataset.batch(b)
+            if ep_mat is not None:
+                yield TF.upsample_levels_moments(src, self.H, self.W, affine=ep_mat[s: s + len(b)])[0], lab
+                continue
             yield TF.upsample_bilinear_u8(src, self.H, self.W, levels=self.levels), lab
 
 

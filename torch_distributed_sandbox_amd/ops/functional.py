@@ -314,13 +314,45 @@ def upsample_bilinear_u8(src: torch.Tensor, H: int, W: int, levels: bool = False
     return _ext.ops().upsample_bilinear_u8(src.contiguous(), int(H), int(W), bool(levels))
 
 
-def upsample_levels_moments(src: torch.Tensor, H: int, W: int):
+def _affine_levels_cpu(src, mats, H: int, W: int):
+    """The affine input op's contract (csrc/kernels/ups_affine.hip) in fp32 torch ops."""
+    B, h, w = src.shape
+    m = mats.float()[:, :, None, None]
+    X = torch.arange(W, dtype=torch.float32) + 0.5
+    Y = (torch.arange(H, dtype=torch.float32) + 0.5)[:, None]
+    u = (m[:, 0] * X + (m[:, 1] * Y + m[:, 2])).clamp(-1, w).nan_to_num(-1.0)  # the kernel's clamp: NaN -> -1
+    v = (m[:, 3] * X + (m[:, 4] * Y + m[:, 5])).clamp(-1, h).nan_to_num(-1.0)
+    i0, j0 = u.floor(), v.floor()
+    ax, ay = u - i0, v - j0
+    s = F.pad(src.float(), (2, 2, 2, 2)).reshape(B, -1)  # zeros around: index + 2
+
+    def tap(j, i):
+        return s.gather(1, ((j + 2) * (w + 4) + i + 2).long().reshape(B, -1)).reshape(B, H, W)
+
+    top = ax * tap(j0, i0 + 1) + (1 - ax) * tap(j0, i0)
+    bot = ax * tap(j0 + 1, i0 + 1) + (1 - ax) * tap(j0 + 1, i0)
+    return (ay * bot + (1 - ay) * top).round_().clamp_(0, 255).to(torch.uint8).unsqueeze(1)
+
+
+def upsample_levels_moments(src: torch.Tensor, H: int, W: int, affine: torch.Tensor | None = None):
     """``upsample_bilinear_u8(src, H, W, levels=True)`` that also forms the batch's x
     autocorrelation partials -- the weight-independent half of BN1's batch statistics in the fused
     ConvNet plan -- in the same pass over the levels (csrc/kernels/ups_moments.hip).  Returns
     ``(levels, partials)``; hand both to the model with ``convnet_fused.attach_input_stats(levels,
-    (partials, None))``.  ``partials`` is None on CPU and for shapes the fused kernel does not take."""
+    (partials, None))``.  ``partials`` is None on CPU and for shapes the fused kernel does not take.
+
+    ``affine``: fp32 ``[B, 6]`` = (m00, m01, m02, m10, m11, m12) per image.  Output pixel (X, Y)
+    then samples the source at ``u = m00 (X + .5) + m01 (Y + .5) + m02``, ``v = m10 (X + .5) +
+    m11 (Y + .5) + m12`` (source pixel indices; the half-pixel -0.5 is folded into m02 / m12),
+    bilinearly with zero padding -- one interpolation at the output resolution, the partials formed
+    from the levels written (csrc/kernels/ups_affine.hip).  ``(w/W, 0, -.5, 0, h/H, -.5)`` is the
+    plain upsample away from its clamped edge.  Shapes the kernel does not take raise."""
+    if affine is None:
+        if not src.is_cuda:
+            return upsample_bilinear_u8(src, H, W, levels=True), None
+        x, part = _ext.ops().upsample_levels_moments(src.contiguous(), int(H), int(W))
+        return x, (part if part.numel() > 0 else None)
     if not src.is_cuda:
-        return upsample_bilinear_u8(src, H, W, levels=True), None
-    x, part = _ext.ops().upsample_levels_moments(src.contiguous(), int(H), int(W))
-    return x, (part if part.numel() > 0 else None)
+        return _affine_levels_cpu(src, affine, int(H), int(W)), None
+    x, part = _ext.ops().upsample_levels_moments_affine(src.contiguous(), affine.contiguous(), int(H), int(W))
+    return x, part.view(-1)

@@ -23,7 +23,7 @@ from datetime import datetime
 import torch
 
 from . import _ext
-from .data import DeviceUpsampleLoader, SyntheticMNIST
+from .data import DeviceUpsampleLoader, RandomAffine, SyntheticMNIST
 from .models import ConvNet, convnet_fused
 from .ops import CrossEntropyLoss, SGD
 from .ops import functional as TF
@@ -77,7 +77,22 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--eval-precision", default="tf32", choices=["tf32", "fp8"],
                    help="conv2 operands of the fused inference plan (evaluation): tf32, the training numerics, "
                         "or fp8 (E4M3 on the block-scaled MFMA)")
+    p.add_argument("--augment-degrees", default=0.0, type=float, metavar="D",
+                   help="random-affine augmentation of the training images: rotation drawn from U(-D, D) degrees")
+    p.add_argument("--augment-translate", default=0.0, type=float, metavar="T",
+                   help="... shift drawn from U(-T, T) of the 28-pixel source edge, per axis")
+    p.add_argument("--augment-scale", default=None, type=float, nargs=2, metavar=("LO", "HI"),
+                   help="... scale drawn from U(LO, HI).  All three off by default; they need --input levels")
     return p
+
+
+def augment_from_args(args) -> RandomAffine | None:
+    """The training loader's augmentation from --augment-*; None when all are off."""
+    deg, tr = float(getattr(args, "augment_degrees", 0.0)), float(getattr(args, "augment_translate", 0.0))
+    sc = getattr(args, "augment_scale", None)
+    if deg == 0.0 and tr == 0.0 and sc is None:
+        return None
+    return RandomAffine(degrees=deg, translate=tr, scale=tuple(sc) if sc is not None else (1.0, 1.0))
 
 
 def resolve_backend(args) -> str:
@@ -220,13 +235,14 @@ def train(gpu: int, args, distributed: bool = False) -> dict:
     levels = getattr(args, "input", "levels") == "levels"
     fused_plan = getattr(args, "mode", "auto") != "layers"
     moments = levels and fused_plan  # the fused plan reads them
+    augment = augment_from_args(args)  # the training loader only: evaluation sees the plain images
     if distributed:
         sampler = DistributedSampler(len(dataset), num_replicas=world, rank=rank)
         loader = DeviceUpsampleLoader(dataset, batch_size, (H, W), device, sampler=sampler, levels=levels,
-                                      moments=moments)
+                                      moments=moments, augment=augment)
     else:
         loader = DeviceUpsampleLoader(dataset, batch_size, (H, W), device, shuffle=True, levels=levels,
-                                      moments=moments)
+                                      moments=moments, augment=augment)
 
     start = datetime.now()
     total_step = len(loader)
@@ -282,6 +298,7 @@ def train(gpu: int, args, distributed: bool = False) -> dict:
     summary = {"rank": rank, "world_size": world, "steps": steps_done, "batch_size": batch_size,
                "image_size": H, "final_loss": float(loss.item()) if loss is not None else None,
                "lr": float(args.lr), **opt_args,
+               "augment": None if augment is None else [augment.degrees, augment.translate, *augment.scale],
                "plan": (f"DDP wrapper ({getattr(model, 'reducer_kind', '?')} reducer, fc grad "
                         f"{model.fc_grad_path()}, overlap_optimizer={model.overlap_optimizer})"
                         if isinstance(model, DistributedDataParallel) else "plain module"),
