@@ -22,8 +22,10 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <string>
 #include <tuple>
 
+#include "kernels/head_inf.h"
 #include "kernels/l1_tiles.h"
 #include "kernels/launchers.h"
 #include "launch_check.h"
@@ -742,6 +744,73 @@ std::tuple<Tensor, Tensor, Tensor> fused_head_forward_aff_ce(const Tensor& ya, c
                                                              const Tensor& labels, const c10::optional<Tensor>& x_out) {
   const auto ws = head_fwd("fused_head_forward_aff_ce", ya, b2, mag, wfc, bfc, P, x_out, finished_aff(aff2), labels);
   return {ws[WS_LOGITS], ws[WS_LOSS], ws[WS_DLOGITS]};
+}
+
+// ---------------------------------------------------------------- inference head on a packed fc weight
+// (kernels/head_inf.hip, geometry in kernels/head_inf.h): fc.weight packed once per evaluation into fp16 or
+// E4M3 fragments, and the head forward that streams ya and that pack once for 1 .. 64 classes and 1 .. 32
+// images on v_mfma_f32_16x16x32_f16.
+int head_inf_kind(const std::string& kind, const char* who) {
+  TORCH_CHECK(kind == "fp16" || kind == "fp8", who, ": kind must be fp16|fp8, got '", kind, "'");
+  return kind == "fp8" ? tds::kHeadInfF8 : tds::kHeadInfF16;
+}
+
+// returns (wpk: the pack, fp16 [pieces * 8] or uint8 [pieces * 8] (E4M3 bytes); wexp int32: the scale
+// exponents, [NC] for fp16 (W_j 2^wexp[j] was rounded), [32, NC] for fp8 (per channel and class))
+std::tuple<Tensor, Tensor> fc_pack_inference(const Tensor& wfc, int64_t P, std::string kind) {
+  const int k = head_inf_kind(kind, "fc_pack_inference");
+  const int64_t Q = P / 2;
+  TORCH_CHECK(P >= 8 && P % 2 == 0 && Q <= 32760, "fc_pack_inference: an even P with 4 <= P/2 <= 32760");
+  TORCH_CHECK(wfc.dim() == 2 && wfc.size(0) >= 1 && wfc.size(0) <= tds::HI_MAX_NC && wfc.size(1) == 32 * Q * Q,
+              "fc_pack_inference: fc.weight must be [1..64, 32*Q*Q]");
+  const int64_t NC = wfc.size(0);
+  need(wfc, at::kFloat, {NC, 32 * Q * Q}, "fc.weight");
+  c10::DeviceGuard guard(wfc.device());
+  const int64_t np = tds::hi_pack_pieces((int)Q, (int)NC);
+  auto wpk = at::empty({np * 8}, wfc.options().dtype(k == tds::kHeadInfF8 ? at::kByte : at::kHalf));
+  auto wexp = k == tds::kHeadInfF8 ? at::empty({32, NC}, wfc.options().dtype(at::kInt))
+                                   : at::empty({NC}, wfc.options().dtype(at::kInt));
+  auto wmx = at::empty({32 * NC}, wfc.options().dtype(at::kInt));
+  const int rc = tds_head_inf_pack(wfc.data_ptr<float>(), wpk.data_ptr(), wexp.data_ptr<int>(),
+                                   reinterpret_cast<uint32_t*>(wmx.data_ptr<int>()), (int)Q, (int)NC, k, stream_of(wfc));
+  TORCH_CHECK(rc == 0, "fc_pack_inference: unsupported shape");
+  check_launches("fc_pack_inference");
+  return {wpk, wexp};
+}
+
+// logits [B, NC] from ya, the BN2 affine and fc_pack_inference's pack.  Everything is checked before
+// anything is allocated.
+Tensor fused_head_forward_inference(const Tensor& ya, const Tensor& aff2, const Tensor& b2,
+                                    const c10::optional<Tensor>& mag, const Tensor& wpk, const Tensor& wexp,
+                                    const c10::optional<Tensor>& bfc, int64_t P, int64_t NC, std::string kind) {
+  const char* who = "fused_head_forward_inference";
+  const int k = head_inf_kind(kind, who);
+  const int64_t Q = P / 2;
+  TORCH_CHECK(P >= 8 && P % 2 == 0 && Q <= 32760, who, ": an even P with 4 <= P/2 <= 32760");
+  TORCH_CHECK(NC >= 1 && NC <= tds::HI_MAX_NC, who, ": 1 <= classes <= 64");
+  TORCH_CHECK(ya.dim() == 3 && ya.size(0) >= 1 && ya.size(0) <= tds::HI_MAX_B, who, ": ya must be [1..32, 32, PB]");
+  const int64_t B = ya.size(0);
+  need(ya, at::kHalf, {B, 32, pb_plane(P)}, "ya");
+  need(aff2, at::kFloat, {64}, "aff2");
+  need(wpk, k == tds::kHeadInfF8 ? at::kByte : at::kHalf, {tds::hi_pack_pieces((int)Q, (int)NC) * 8}, "fc pack");
+  if (k == tds::kHeadInfF8) need(wexp, at::kInt, {32, NC}, "fc pack exponents");
+  else need(wexp, at::kInt, {NC}, "fc pack exponents");
+  const float* bf = optf(bfc, NC, "fc.bias");
+  const TdsYaDec yd = ya_dec(b2, mag);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(ya.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(wpk.data_ptr()) % 16 == 0,
+              who, ": ya and the pack must be 16-B aligned");
+  TORCH_CHECK(aff2.device() == ya.device() && b2.device() == ya.device() && wpk.device() == ya.device() &&
+                  wexp.device() == ya.device() && (bf == nullptr || bfc->device() == ya.device()),
+              who, ": every tensor must be on ya's device");
+  c10::DeviceGuard guard(ya.device());
+  auto partial = at::empty({tds_head_inf_partials((int)B, (int)Q, (int)NC)}, ya.options().dtype(at::kDouble));
+  auto logits = at::empty({B, NC}, ya.options().dtype(at::kFloat));
+  const int rc = tds_head_inf_fwd(ya_out(ya), yd, wpk.data_ptr(), wexp.data_ptr<int>(), bf, aff2.data_ptr<float>(),
+                                  partial.data_ptr<double>(), logits.data_ptr<float>(), (int)B, (int)Q, (int)NC, k,
+                                  stream_of(ya));
+  TORCH_CHECK(rc == 0, who, ": launcher refused (", rc, ")");
+  check_launches(who);
+  return logits;
 }
 
 // The head forward in channel-range launches (the activation exchange's column groups, parallel/
@@ -1750,6 +1819,10 @@ TORCH_LIBRARY_FRAGMENT(tdsa, m) {
   m.def("fused_head_forward_aff(Tensor ya, Tensor aff2, Tensor b2, Tensor? mag, Tensor wfc, Tensor? bfc, int P, "
         "Tensor(a!)? x_out=None) -> Tensor",
         &fused_head_forward_aff);
+  m.def("fc_pack_inference(Tensor wfc, int P, str kind) -> (Tensor, Tensor)", &fc_pack_inference);
+  m.def("fused_head_forward_inference(Tensor ya, Tensor aff2, Tensor b2, Tensor? mag, Tensor wpk, Tensor wexp, "
+        "Tensor? bfc, int P, int NC, str kind) -> Tensor",
+        &fused_head_forward_inference);
   m.def("fused_head_forward_aff_ce(Tensor ya, Tensor aff2, Tensor b2, Tensor? mag, Tensor wfc, Tensor? bfc, int P, "
         "Tensor labels, "
         "Tensor(a!)? x_out=None) -> (Tensor, Tensor, Tensor)",

@@ -334,6 +334,16 @@ int tds_head_wide_upd(const unsigned short* ya_all, const float* rec, int nranks
                       float* out, int B, int Q, int NC, float scale, float lr, int mode, hipStream_t st,
                       const TdsHeadMom* hm = nullptr);
 
+// ---- head_inf.hip (the inference plan's fc head on a packed fp16 / E4M3 weight, fp16 MFMA; geometry in
+// head_inf.h).  kind: HeadInfKind (0 fp16, 1 fp8); 1 <= NC <= 64, 1 <= B <= 32, Q >= 4; other shapes: -1
+// wpk: hi_pack_pieces(Q, NC) pieces of 16 / 8 bytes, wexp: hi_exp_count(NC, kind) scale exponents, wmx:
+// 32 * NC scratch words (max |W| per class and channel)
+int tds_head_inf_pack(const float* Wfc, void* wpk, int* wexp, uint32_t* wmx, int Q, int NC, int kind, hipStream_t st);
+int64_t tds_head_inf_partials(int B, int Q, int NC);  // doubles of tds_head_inf_fwd's workspace
+// logits [B][NC] from ya, the pack and the BN2 affine, finished inside the launch
+int tds_head_inf_fwd(const unsigned short* ya, TdsYaDec yd, const void* wpk, const int* wexp, const float* bias,
+                     const float* aff2, double* partial, float* logits, int B, int Q, int NC, int kind, hipStream_t st);
+
 // ---- zs_exchange.hip (zero-suppressed fc-input rows, parallel/zs.py)
 int64_t tds_zs_npages(int64_t n);
 // meta [npages * 65] (offsets + mask words), counts [npages] scratch, vals [cap] (dropped past

@@ -35,6 +35,7 @@ from ..ops import modules as M
 
 IMAGE_SHAPE = (3000, 3000)
 INFERENCE_PRECISIONS = ("tf32", "fp8")
+INFERENCE_FC_PRECISIONS = ("fp32", "fp16", "fp8")
 LEVEL_SCALE = 1.0 / 255.0  # fp32(1/255): the scale ToTensor and the upsample kernel apply to uint8 levels
 
 
@@ -53,7 +54,7 @@ def fc_in_features(image_shape, channels: int = 32) -> int:
 
 class ConvNet(nn.Module):
     def __init__(self, num_classes: int = 10, image_shape=IMAGE_SHAPE, device=None, mode: str = "auto",
-                 inference_precision: str = "tf32"):
+                 inference_precision: str = "tf32", inference_fc_precision: str = "fp32"):
         super().__init__()
         self.image_shape = tuple(image_shape)
         self.layer1 = nn.Sequential(
@@ -83,6 +84,30 @@ class ConvNet(nn.Module):
             raise ValueError(
                 f"inference_precision must be {'|'.join(INFERENCE_PRECISIONS)}, got {inference_precision!r}")
         self.inference_precision = inference_precision
+        # the fc weight's type in the fused inference plan's head: "fp32", the training head on fc.weight
+        # itself, or a one-time pack of it in "fp16" / "fp8" (E4M3, weight-only) streamed by the inference
+        # head on the fp16 MFMA (csrc/kernels/head_inf.hip; opt-in, independent of inference_precision).
+        # The pack is cached here across eval forwards (convnet_fused._fc_pack).  A non-empty
+        # TDS_INFERENCE_FC_PRECISION overrides the argument.
+        env_fc = os.environ.get("TDS_INFERENCE_FC_PRECISION", "").strip()
+        if env_fc:
+            inference_fc_precision = env_fc
+        if inference_fc_precision not in INFERENCE_FC_PRECISIONS:
+            raise ValueError(
+                f"inference_fc_precision must be {'|'.join(INFERENCE_FC_PRECISIONS)}, got {inference_fc_precision!r}")
+        self.inference_fc_precision = inference_fc_precision
+        self._fc_pack = None
+
+    # the cached fc pack describes the weight it was made from: training and loading change the weight
+    # (the fused steps through raw pointers, without a version bump)
+    def train(self, mode: bool = True):
+        if mode:
+            self._fc_pack = None
+        return super().train(mode)
+
+    def load_state_dict(self, *args, **kwargs):
+        self._fc_pack = None
+        return super().load_state_dict(*args, **kwargs)
 
     # ------------------------------------------------------------------ plans
     def _forward_layers(self, x):

@@ -66,10 +66,14 @@ def supported_inference(model, x) -> bool:
     under ``no_grad``."""
     if not (x.is_cuda and not model.training and not torch.is_grad_enabled()):
         return False
-    return _supported_config(model, x)
+    return _supported_config(model, x, wide_batch=32 if _fc_kind(model) != "fp32" else 16)
 
 
-def _supported_config(model, x) -> bool:
+def _fc_kind(model) -> str:
+    return getattr(model, "inference_fc_precision", "fp32")
+
+
+def _supported_config(model, x, wide_batch: int = 16) -> bool:
     # uint8: ToTensor's levels, x = levels / 255 folded into conv1 (models/convnet.py to_image)
     if x.dim() != 4 or x.shape[1] != 1 or x.dtype not in (torch.float32, torch.uint8):
         return False
@@ -87,7 +91,8 @@ def _supported_config(model, x) -> bool:
     if c1.bias is None or c2.bias is None or model.fc.out_features > 64 or model.fc.bias is None:
         return False
     # 11 .. 64 classes: the wide head (csrc/kernels/head_wide.hip) holds the batch in one 16-row MFMA tile
-    if model.fc.out_features > 10 and B > 16:
+    # (wide_batch = 32: the inference head on a packed weight, csrc/kernels/head_inf.hip, takes two tiles)
+    if model.fc.out_features > 10 and B > wide_batch:
         return False
     if any(p.dtype != torch.float32 or not p.is_cuda for p in model.parameters()):
         return False
@@ -187,7 +192,7 @@ _ZERO = {}
 # counters the tests read: forward passes that applied the exchange's weight update in the head kernel,
 # and layer-1 forwards that took x moments precomputed by the input pipeline
 STATS = {"precomputed_input_moments": 0, "head_fused_ce": 0, "head_range_launches": 0, "head_wide": 0,
-         "inference_fp8": 0}
+         "inference_fp8": 0, "inference_fc_packs": 0, "inference_fc_head": 0}
 
 
 def _zero_scalar(device, dtype):
@@ -516,6 +521,7 @@ def _pack_in_layer1(w2, x, link, link1):
 
 
 def forward(model, x):
+    model._fc_pack = None  # the step changes fc.weight (through raw pointers): the inference plan's pack is stale
     conv1, bn1 = model.layer1[0], model.layer1[1]
     conv2, bn2 = model.layer2[0], model.layer2[1]
     fc = model.fc
@@ -582,6 +588,9 @@ def forward(model, x):
 # ConvNet(inference_precision="fp8") swaps the two conv2 launches for their E4M3 forms (conv2_pack_fp8,
 # fused_conv2_forward_inference_fp8: v_mfma_scale_f32_16x16x128_f8f6f4); ya's format and the head are
 # the same, the decode words in mag describe the FP8 kernel's scales.
+# ConvNet(inference_fc_precision="fp16" | "fp8") swaps the head for the inference head on a packed fc
+# weight (fc_pack_inference once per weight, cached on the model; fused_head_forward_inference:
+# csrc/kernels/head_inf.hip), which also takes 11 .. 64 classes with 17 .. 32 images.
 _INFERENCE_MAG = 48  # the bounds conv2_pack zeroes (33 words), the scales at kMagScales = 40 .. 43, p1's FP8 scale at 45
 
 
@@ -614,7 +623,26 @@ def forward_inference(model, x):
     param_fence.wait(fc.bias)
     if upd is not None:
         upd()  # the whole deferred update, before the weight is read
+    kind = _fc_kind(model)
+    if kind != "fp32":
+        wpk, wexp = _fc_pack(model, ops, kind, p1.shape[1])
+        STATS["inference_fc_head"] += 1
+        return ops.fused_head_forward_inference(ya, aff2, conv2.bias, mag, wpk, wexp, fc.bias, p1.shape[1],
+                                                fc.out_features, kind)
     if fc.out_features > 10:
         return ops.fused_head_wide_forward_aff(ya, aff2, conv2.bias, mag, fc.weight, fc.bias, p1.shape[1])[0]
     return ops.fused_head_forward_aff(ya, aff2, conv2.bias, mag, fc.weight, fc.bias, p1.shape[1], None)
 
+
+def _fc_pack(model, ops, kind, P):
+    """fc.weight's inference pack (ops.fc_pack_inference), cached on the model across eval forwards:
+    evaluate() runs many batches on one weight.  The key holds the weight's address and version; the
+    steps that change it without a version bump (the fused backward, the exchange's update kernels)
+    run behind the training plan's forward, which drops the cache, as do train() and load_state_dict."""
+    w = model.fc.weight
+    key = (w.data_ptr(), w._version, kind, P)
+    cached = getattr(model, "_fc_pack", None)
+    if cached is None or cached[0] != key:
+        cached = model._fc_pack = (key, ops.fc_pack_inference(w.detach().contiguous(), P, kind))
+        STATS["inference_fc_packs"] += 1
+    return cached[1]

@@ -77,6 +77,9 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--eval-precision", default="tf32", choices=["tf32", "fp8"],
                    help="conv2 operands of the fused inference plan (evaluation): tf32, the training numerics, "
                         "or fp8 (E4M3 on the block-scaled MFMA)")
+    p.add_argument("--eval-fc-precision", default="fp32", choices=["fp32", "fp16", "fp8"],
+                   help="the fc weight of the fused inference plan's head (evaluation): fp32, the training head, or a "
+                        "one-time fp16 / fp8 (E4M3, weight-only) pack streamed on the fp16 MFMA")
     p.add_argument("--augment-degrees", default=0.0, type=float, metavar="D",
                    help="random-affine augmentation of the training images: rotation drawn from U(-D, D) degrees")
     p.add_argument("--augment-translate", default=0.0, type=float, metavar="T",
@@ -209,7 +212,8 @@ def train(gpu: int, args, distributed: bool = False) -> dict:
     torch.manual_seed(0)
     H = W = args.image_size
     model = ConvNet(num_classes=args.num_classes, image_shape=(H, W), device=device, mode=args.mode,
-                    inference_precision=getattr(args, "eval_precision", "tf32"))
+                    inference_precision=getattr(args, "eval_precision", "tf32"),
+                    inference_fc_precision=getattr(args, "eval_fc_precision", "fp32"))
     batch_size = args.batch_size
     criterion = CrossEntropyLoss()
     opt_args = {"momentum": float(getattr(args, "momentum", 0.0)), "weight_decay": float(getattr(args, "weight_decay", 0.0)),
